@@ -16,7 +16,8 @@ its rows out to its chunks the same way: every chunk then sees the whole image (
 reference's random pixel batches, instead of a band of empty background at the top of the frame whose masked loss terms have no
 positive element (their mean over an empty selection is NaN in the reference, engine/model.py:602, and would poison the step).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set-up, --warmup steps, --steps timed steps, the
+outputs of the last one if --dump-outputs is given, the line.  Everything else the benchmark measures or checks runs with --full.
 """
 import argparse
 import json
@@ -72,6 +73,11 @@ def parse():
                          "per-GPU shape -- a field on the multiresolution hash encoding (no reference counterpart), 1024x1024, 256 samples/ray (--res / --spp default to those).  "
                          "multi: BASELINE configs[3]'s per-GPU shape -- the fg field of a 10-video category model (num_inst=10: per-instance codes in every CondMLP, "
                          "fg_motion comp_skel-quad_dense: shared quadruped skeleton + dense post-warp), a frame pair of one of the videos")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: the forward-only rate, the sustained rate, PSNR against the reference's "
+                                                        "renders, the fp32 leg, the other configurations, in-run PMC traffic, the per-kernel roofline and the CPU "
+                                                        "baseline.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (its loss terms, the updated parameters "
+                                                                        "and their gradient) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="only the timed training step: no forward-only rate, no PSNR, no fp32 leg (used by the fp32 leg's own child run)")
     ap.add_argument("--no-fp32-leg", action="store_true", help="skip the short fp32 run of the same step that the default bf16 run appends (fp32_leg)")
@@ -80,7 +86,7 @@ def parse():
                                                                "(TrainLoop.capture_step: every chunk + prologue + optimizer in two graph launches per step)")
     ap.add_argument("--hash-f32-table-grad", action="store_true", help="--config hash: every level's table gradient through fp32 atomics (the round-5 form) instead of packed fp16 atomics on the hashed levels")
     ap.add_argument("--hash-no-compact", action="store_true", help="--config hash: evaluate the field on every sample (the round-5 form) instead of the inside-box samples only")
-    ap.add_argument("--sustain-steps", type=int, default=75, help="default single-GPU fg run: steps the loop is continued for behind the timed region (the sustained rate, reported beside the headline)")
+    ap.add_argument("--sustain-steps", type=int, default=75, help="--full single-GPU fg run: steps the loop is continued for behind the timed region (the sustained rate, reported beside the headline)")
     ap.add_argument("--cpu-rays", type=int, default=4096, help="rays per frame of one CPU-baseline pass: 2 x 4,096 = one 8,192-ray chunk of the reference's chunking of configs[1]")
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group and run the gradient all-reduce even at world size 1 "
                                                               "(exercises init order, graph capture next to RCCL's buffers and the collective call on a 1-GPU box)")
@@ -390,7 +396,7 @@ def fp32_leg(a):
     + 2 timed steps in a child process once this one has given its device memory back.  fp32 is the precision the reference computes in
     and the one the 1e-4 parity tests run: its throughput belongs next to the bf16 headline."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--dtype", "f32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras",
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--dtype", "f32", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras",
            "--res", str(a.res), "--spp", str(a.spp)]
     tmo = EXTRAS.timeout(600)
     if tmo is None:
@@ -413,9 +419,10 @@ def other_configs_legs():
     out = {}
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     for cfg in ("config0_shape", "comp", "multi", "hash"):
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", cfg, "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extras"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", cfg, "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extras"]
         if cfg == "config0_shape":  # BASELINE configs[0]'s shape through the fg loop: a 64 x 64 crop of the frame pair, 64 samples/ray = 8,192 rays per step (launch-bound: 50 steps)
-            cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--res", "64", "--spp", "64", "--chunk-rows", "64", "--steps", "50", "--warmup", "5", "--no-cpu-baseline", "--no-extras"]
+            cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--res", "64", "--spp", "64", "--chunk-rows", "64", "--steps", "50", "--warmup", "5", "--full",
+                   "--no-cpu-baseline", "--no-extras"]
         t0 = time.perf_counter()
         tmo = EXTRAS.timeout(420)
         if tmo is None:
@@ -701,10 +708,13 @@ def hash_main(a):
         last = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    _lib.PROF = {}
-    for hxy, tgt in inputs[:4]:
-        chunk(hxy, tgt)
-    torch.cuda.synchronize()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"loss_last_chunk": last, "params": opt.flat, "grads": opt.flat_grad})
+    if a.full:
+        _lib.PROF = {}
+        for hxy, tgt in inputs[:4]:
+            chunk(hxy, tgt)
+        torch.cuda.synchronize()
     prof = _lib.prof_summary()
     _lib.PROF = None
     rays = 2 * res * res
@@ -752,6 +762,25 @@ def hash_main(a):
 def fail(msg, code=2):
     print("bench.py: " + msg, file=sys.stderr)
     sys.exit(code)
+
+
+DUMP_BYTES = 60 * 10**6  # --dump-outputs: the arrays' payload, below the 64 MB cap with the .npy headers
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array of the last timed step, so that two builds can be compared output for output.  When the
+    arrays hold more than DUMP_BYTES, each keeps its share of that as a sample of its elements drawn with a fixed seed: the same elements for the
+    same shapes in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values()) * 4
+    for name, t in arrays.items():
+        x = t.detach().float()
+        if total > DUMP_BYTES:
+            keep = x.numel() * DUMP_BYTES // total
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            x = x.reshape(-1)[idx.to(x.device)]
+        np.save(os.path.join(path, name + ".npy"), x.cpu().numpy())
 
 
 def launch_ranks(a):
@@ -827,6 +856,10 @@ def main():
         a.gpus = int(env_world) if env_world else 1
     if a.gpus < 1:
         fail("--gpus must be >= 1")
+    if a.steps < 1:
+        fail("--steps must be >= 1")
+    if a.dump_outputs and a.dry_step:
+        fail("--dump-outputs needs a run on the GPU: --dry-step computes no outputs")
     if a.backend == "gloo" and not (a.dry_step or a.share_gpu):
         fail("--backend gloo runs no GPU work: use it with --dry-step, or with --share-gpu for a functional multi-rank run on fewer GPUs than ranks")
     if a.share_gpu and a.backend != "gloo":
@@ -1124,7 +1157,7 @@ def rank_main(a):
     # through one first-order backward, compositing) of the same rays.  Measured before the training graph is captured
     # (its 150 GiB private pool would leave the allocator thrashing), half a training chunk per call.
     eval_result = None
-    if world == 1 and rank == 0 and not comp and not multi and not a.trace and not a.no_extras:
+    if a.full and world == 1 and rank == 0 and not comp and not multi and not a.trace and not a.no_extras:
         try:
             P_e, fr_e = make_problem(res, dev)
             inputs_e = [chunk_inputs(res, None, rows, dev, seed=100 + i) for i, rows in enumerate(plan["chunks"])]
@@ -1151,7 +1184,7 @@ def rank_main(a):
             dist.barrier()
         torch.cuda.synchronize()
 
-    if graph is None:
+    if graph is None and a.full:
         _lib.PROF = {}
     sync()
     t0 = time.perf_counter()
@@ -1162,12 +1195,14 @@ def rank_main(a):
     prof_src = "HIP events around every launch of the family during the timed steps"
     n_prof_chunks = len(inputs) * a.steps
     loss_last = float(last[12])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"loss_terms_last_chunk": last, "params": opt.flat, "grads": opt.flat_grad})
     peak_hbm = torch.cuda.max_memory_allocated()
     # The package sits at its power cap under the chain kernels: the longer the run, the warmer the part and the lower the sustained clock (DESIGN.md
     # section 5: 25-step runs 695-705 ms, a 200-step run 715 ms on the same kernels).  The headline is the K steps the contract times; the sustained rate is
-    # reported BESIDE it: the same loop continued for --sustain-steps more steps (default single-GPU fg run only), timed on its own.
+    # reported BESIDE it: the same loop continued for --sustain-steps more steps (--full single-GPU fg run only), timed on its own.
     sustained = None
-    n_sus = a.sustain_steps if (world == 1 and a.config == "fg" and not a.no_extras and not a.emulate_rank_of and not a.trace and graph_ok(loop, graph)) else 0
+    n_sus = a.sustain_steps if (a.full and world == 1 and a.config == "fg" and not a.no_extras and not a.emulate_rank_of and not a.trace and graph_ok(loop, graph)) else 0
     if n_sus > 0:
         sync()
         ts0 = time.perf_counter()
@@ -1182,7 +1217,7 @@ def rank_main(a):
     launch_mode = ("two hipGraph replays per optimizer step (all chunks + prologue | check_grad + AdamW + repack)" if loop.graph_a is not None else
                    "hipGraph replay per chunk" if graph is not None else "eager")
     n_skipped = int(opt.steps - int(opt.dev_step))  # steps check_grad discarded (0 on a healthy run)
-    if graph is not None:
+    if graph is not None and a.full:
         # the eager re-run below needs the memory the graph's private pool holds
         last = graph = None
         loop.release_graph()
@@ -1294,23 +1329,24 @@ def rank_main(a):
         # the headline is complete here: leave a copy on stderr (and under /tmp) BEFORE the extras run, so that a run cut off inside them
         # (driver timeout) has not lost the measurement.  stdout still carries exactly one line, written at the very end.
         EXTRAS.start()  # the budget covers what follows, not the headline run above
-        try:
-            head = json.dumps({k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "dtype", "loss_last_chunk", "params_finite")})
-            print("[bench headline, extras still to run] " + head, file=sys.stderr, flush=True)
-            with open("/tmp/lab4d_bench_headline.json", "w") as fh:
-                fh.write(json.dumps(out, default=str) + "\n")
-        except Exception:
-            pass
+        if a.full:
+            try:
+                head = json.dumps({k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "dtype", "loss_last_chunk", "params_finite")})
+                print("[bench headline, extras still to run] " + head, file=sys.stderr, flush=True)
+                with open("/tmp/lab4d_bench_headline.json", "w") as fh:
+                    fh.write(json.dumps(out, default=str) + "\n")
+            except Exception:
+                pass
         if comp:
             out["metric"] = "rendered rays/sec (fwd+bwd), fg+bg composite at 512\u00b2 (BASELINE configs[2] per-GPU shape; not the headline metric)"
         if multi:
             out["metric"] = "rendered rays/sec (fwd+bwd), 10-instance category model at 512\u00b2 (BASELINE configs[3] per-GPU shape; not the headline metric)"
-        if world == 1 and not comp and not multi and not a.no_extras:
+        if a.full and world == 1 and not comp and not multi and not a.no_extras:
             try:
                 out["psnr_vs_ref_db"] = psnr_vs_reference(dev)
             except Exception as e:
                 out["psnr_vs_ref_db"] = {"error": repr(e)[:200]}
-        if world == 1 and a.dtype == "bf16" and a.config == "fg" and not (a.no_extras or a.no_fp32_leg or a.emulate_rank_of or a.trace):
+        if a.full and world == 1 and a.dtype == "bf16" and a.config == "fg" and not (a.no_extras or a.no_fp32_leg or a.emulate_rank_of or a.trace):
             # the path that carries the 1e-4 parity claim, at the same shape, in the same line (the reference computes in fp32 only)
             loop = opt = params = inputs = step = None
             import gc
@@ -1334,7 +1370,7 @@ def rank_main(a):
             for r_ in [roofline] + roofline.get("others", []):
                 r_["traffic"] = pmc.get(r_["kernel"], {}).get("hbm_bytes_per_launch")
             roofline["traffic_source"] = pmc.get("_source") if roofline["traffic"] else None
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(res, spp, a.cpu_rays, a.config)
     if use_dist:
         dist.destroy_process_group()

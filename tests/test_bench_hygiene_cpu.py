@@ -24,6 +24,22 @@ def test_cpu_baseline_protocol_on_a_tiny_sample():
     assert "2 frames x 48 rays x 16 samples" in out["sample"] and "timed pass" in out["sample"]
 
 
+def test_dump_outputs_float32_under_the_cap_and_the_same_sample_every_run(tmp_path, monkeypatch):
+    import numpy as np
+    arrays = {"loss": torch.tensor([0.5, 1.5], dtype=torch.float64), "params": torch.randn(40, 25, generator=torch.Generator().manual_seed(1))}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for name, t in arrays.items():  # below the cap: every element, in its shape
+        x = np.load(tmp_path / "whole" / (name + ".npy"))
+        assert x.dtype == np.float32 and np.array_equal(x, t.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2000)
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    got = {name: np.load(tmp_path / "a" / (name + ".npy")) for name in arrays}
+    assert sum(x.nbytes for x in got.values()) <= 2000 and all(x.dtype == np.float32 for x in got.values())
+    assert all(np.array_equal(x, np.load(tmp_path / "b" / (name + ".npy"))) for name, x in got.items())
+    assert 0 < got["params"].size < 1000 and np.isin(got["params"], arrays["params"].numpy()).all()
+
+
 def test_distinct_indices_never_returns_uninitialised_slots():
     g = torch.Generator().manual_seed(0)
     x = bench.distinct_indices(5000, 1024, "cpu", g)
