@@ -34,8 +34,8 @@ const char* lab4d_last_error(void);
 int lab4d_version(void);
 /* returns the gfx arch string the library was compiled for ("gfx950") */
 const char* lab4d_arch(void);
-/* the kernel-experiment macros (LAB4D_ABL_*, LAB4D_WSABL_*, LAB4D_WS_TRACE, ... with the LAB4D_ prefix dropped, blank separated) the library was
- * compiled with; "" for the shipped build.  Most of them give WRONG results (timing ablations): callers refuse a library that reports any. */
+/* the kernel-experiment macros (LAB4D_WSABL_NOST, LAB4D_ABL_WGRAD_L2 with the LAB4D_ prefix dropped, blank separated) the library was
+ * compiled with; "" for the shipped build.  Both give WRONG results (timing ablations): callers refuse a library that reports any. */
 const char* lab4d_build_flags(void);
 
 /* ------------------------------------------------------------------------------------------

@@ -45,17 +45,16 @@ def _newer(src, dst):
 
 def build(force=False, verbose=True):
     """hipcc --offload-arch=gfx950 every csrc/*.hip, link liblab4d_hip.so in-tree."""
-    extra = os.environ.get("LAB4D_HIPCC_EXTRA", "")
-    if "amdgpu-mfma-vgpr-form" in extra and "LAB4D_MFMA_VGPR_FORM" not in extra:
+    if "amdgpu-mfma-vgpr-form" in os.environ.get("LAB4D_HIPCC_EXTRA", ""):
         # csrc/mlp_kernels.hpp acc_fence_if: the one-wave-per-SIMD chain kernels drop the MFMA -> inline-asm hazard fence because their accumulators live in
         # AGPRs (a compiler-visible v_accvgpr_read sits in between); with the MFMA results forced into VGPRs that is no longer true (ADVICE r04)
-        raise RuntimeError("LAB4D_HIPCC_EXTRA passes -amdgpu-mfma-vgpr-form without -DLAB4D_MFMA_VGPR_FORM: the accumulator hazard fence would be dropped")
+        raise RuntimeError("LAB4D_HIPCC_EXTRA passes -amdgpu-mfma-vgpr-form: the chain kernels' accumulator hazard fence assumes AGPR accumulators")
     os.makedirs(BUILD_DIR, exist_ok=True)
     # The compile flags are part of the staleness key (ADVICE r05): an experiment build (-DLAB4D_ABL_* ...) in this BUILD_DIR followed by a
     # default build must not leave objects of the other flag set behind -- rebuilds are per object and mtime-based, and lab4d_build_flags()
     # only reports what runtime.hip's own object saw.  A stamp of the full flag set lives beside the objects; when it differs, everything is rebuilt.
     stamp_path = os.path.join(BUILD_DIR, "flags.stamp")
-    stamp = "\n".join([HIPCC] + CFLAGS + ["--inst--"] + (MLP_INST_FLAGS if os.environ.get("LAB4D_NO_INST_FLAGS", "0") != "1" else [])) + "\n"
+    stamp = "\n".join([HIPCC] + CFLAGS + ["--inst--"] + MLP_INST_FLAGS) + "\n"
     try:
         with open(stamp_path) as fh:
             stale_flags = fh.read() != stamp
@@ -76,9 +75,7 @@ def build(force=False, verbose=True):
 
     def cc(job):
         src, obj = job
-        # (round 5: the instantiation flags used to be dropped silently whenever LAB4D_HIPCC_EXTRA was set -- an experiment build then differed from
-        # the shipped one in more than its -D; LAB4D_NO_INST_FLAGS=1 is the explicit way to build without them)
-        inst = os.path.basename(src).startswith("mlp_inst_") and os.environ.get("LAB4D_NO_INST_FLAGS", "0") != "1"
+        inst = os.path.basename(src).startswith("mlp_inst_")
         cmd = [HIPCC] + CFLAGS + (MLP_INST_FLAGS if inst else []) + ["-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:

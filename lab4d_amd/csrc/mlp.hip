@@ -324,11 +324,6 @@ __device__ __forceinline__ void wait_vmcnt() {
 // 8 waves: the same 32-KiB stages in the same LDS ring, but two waves per SIMD (128-160 accumulator registers each instead of
 // 256), so the DMA issue, the LDS reads and the barrier wait of one wave overlap the MFMAs of the other, and a 320-column
 // operand (the skip layer: embedding + activation) fits ONE job (TN = 5) instead of two that each re-read dZ.
-#ifdef LAB4D_ABL_WGRAD4
-#define LAB4D_WGRAD_NB5 0
-#else
-#define LAB4D_WGRAD_NB5 1
-#endif
 // WC = columns of the wave grid (2: the layers; 4: the <= 32-row heads, MT = 1 -- every wave owns the one row tile and a quarter of
 // the 64 NBW columns, the default since round 3; LAB4D_WGRAD_HEAD_DMA=0 selects the pre-DMA kernel).
 template <int MT, int NBW, int NW = 4, int WC = 2>
@@ -761,7 +756,7 @@ extern "C" int lab4d_mlp_wgrad_mapped(int net, int layer, int precision, int S, 
   const bool dma = precision == LAB4D_PREC_BF16 && (mo_tiles == 8 || mo_tiles == 4 || mo_tiles == 2 || (mo_tiles == 1 && head_dma && Kt <= 256));
   // K = 320 (skip layer): one 320-column job with the 8-wave kernel of the 256-row layers, 192 + 128 otherwise
   const int nbw = (dma && mo_tiles == 1) ? (Kt <= 128 ? 2 : 4)  // heads: 1 x 4 wave grid, 128 or 256 columns per workgroup
-                  : Kt <= 64 ? 1 : (Kt <= 128 ? 2 : (Kt <= 192 ? 3 : (Kt <= 256 ? 4 : (LAB4D_WGRAD_NB5 && mo_tiles == 8 && Kt <= 320 ? 5 : 3))));
+                  : Kt <= 64 ? 1 : (Kt <= 128 ? 2 : (Kt <= 192 ? 3 : (Kt <= 256 ? 4 : (mo_tiles == 8 && Kt <= 320 ? 5 : 3))));
   const int TM = mo_tiles >= 4 ? 4 : (mo_tiles >= 2 ? 2 : 1);
   const int ob_n = dma ? 1 : (big ? div_up(mo_tiles, 8) : div_up(mo_tiles, TM));
   const int kb_n = dma ? div_up(Kt, 64 * nbw) : (big ? div_up(nk_tiles, 8) : div_up(nk_tiles, 4));
@@ -801,11 +796,7 @@ extern "C" int lab4d_mlp_wgrad_mapped(int net, int layer, int precision, int S, 
 #define WGD_NB(MTV) do { if (nbw == 1) WGD(MTV, 1); else if (nbw == 2) WGD(MTV, 2); else if (nbw == 3) WGD(MTV, 3); else WGD(MTV, 4); } while (0)
   if (dma) {
     if (mo_tiles == 8) {
-#ifdef LAB4D_ABL_WGRAD4
-      WGD_NB(8);
-#else
       if (nbw == 1) WGD8(1); else if (nbw == 2) WGD8(2); else if (nbw == 3) WGD8(3); else if (nbw == 4) WGD8(4); else WGD8(5);
-#endif
     } else if (mo_tiles == 4) WGD_NB(4); else if (mo_tiles == 2) WGD_NB(2);
     else if (nbw == 2) hipLaunchKernelGGL((k_mlp_wgrad_dma<1, 2, 4, 4>), grid, block, 0, st, (const unsigned short*)dz, (const unsigned short*)emb,
                                           (const unsigned short*)act_prev, L.ke, L.kin, S_pad, chunk, spf, cpf, dW, db_arg, wm);

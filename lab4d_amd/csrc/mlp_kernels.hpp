@@ -93,14 +93,10 @@ __device__ __forceinline__ void acc_fence(f32x16_t& c) {
 
 // Kernels built for ONE wave per SIMD use more than 256 registers, so their accumulators live in AGPRs and a compiler-visible v_accvgpr_read
 // (whose hazards the compiler handles) always sits between the MFMA and the asm consumer: the 40 NOP states per step are only needed by the
-// two-waves-per-SIMD builds, or when the MFMA results are forced into VGPRs (-mllvm -amdgpu-mfma-vgpr-form: define LAB4D_MFMA_VGPR_FORM).
+// two-waves-per-SIMD builds (which is why _lib.build refuses -mllvm -amdgpu-mfma-vgpr-form, forcing the MFMA results into VGPRs).
 template <bool OCC2>
 __device__ __forceinline__ void acc_fence_if(f32x16_t& c) {
-#if defined(LAB4D_FENCE_ALWAYS) || defined(LAB4D_MFMA_VGPR_FORM)
-  acc_fence(c);
-#else
   if constexpr (OCC2) acc_fence(c);  // round 4: -2 % of the step together with the scheduler flag of _lib.MLP_INST_FLAGS (profiles/r04_flag_variants.json)
-#endif
 }
 
 // feature (row) held by accumulator register r of lane-half h inside a 32-row tile
@@ -127,43 +123,16 @@ __device__ __forceinline__ void gst16(GLOBAL_AS void* p, unsigned int x, unsigne
   u32x4_t v = {x, y, z, w};
   // streaming (nt) store: stored activations / dZ / embeddings are written once and read once, much later, by the weight-gradient
   // kernels -- measured -6.5 % on the training-mode forward and -6.3 % on the backward chain against plain stores
-#ifdef LAB4D_ABL_PLAINSTORE
-  *(GLOBAL_AS u32x4_t*)p = v;
-#elif defined(LAB4D_ST_AGPR)  // kernel experiment: the store takes its data from accumulation registers
-  asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(p), "a"(v) : "memory");
-#else
   __builtin_nontemporal_store(v, (GLOBAL_AS u32x4_t*)p);
-#endif
-}
-// the same store as (wave-uniform tile base, per-lane byte offset): -DLAB4D_ST_BUF issues it as buffer_store_dwordx4 with the base in an
-// SGPR resource descriptor (kernel experiment); otherwise identical to gst16(base + off, ..)
-__device__ __forceinline__ void gst16o(GLOBAL_AS char* base, unsigned off, unsigned int x, unsigned int y, unsigned int z, unsigned int w) {
-#ifdef LAB4D_ST_BUF
-  u32x4_t v = {x, y, z, w};
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000);
-  __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, (int)off, 0, 2);
-#else
-  gst16(base + off, x, y, z, w);
-#endif
 }
 
 // 16-byte A group load: the packed block of (mt, g) is 1 KiB, lane-linear.
 // `base`, G and mt are wave-uniform: the tile base stays in SGPRs and the load uses the saddr + 32-bit lane offset +
 // immediate form (64-bit per-lane addresses cost two VGPRs per group and, under the register pressure of this kernel,
 // were being spilled to scratch and reloaded one by one).
-// Kernel experiments for the next round: the weight stream never hits in the 32-KiB vector L1 (a layer is
-// 128 KiB), so it can be told not to allocate there -- -DLAB4D_A_NT: nt bit (streaming); -DLAB4D_A_SC: sc0 sc1 (system-coherent, L1 bypass).
 __device__ __forceinline__ uint4 load_a(const GLOBAL_AS void* base, int G, int mt, int g, int lane) {
   const GLOBAL_AS char* tile = (const GLOBAL_AS char*)base + (size_t)(unsigned)(mt * G) * 1024u;
-#if defined(LAB4D_A_NT)
-  const u32x4_t v = __builtin_nontemporal_load((const GLOBAL_AS u32x4_t*)(tile + (unsigned)(g * 1024 + lane * 16)));
-  return make_uint4(v.x, v.y, v.z, v.w);
-#elif defined(LAB4D_A_SC)
-  const u32x4_t v = *(const volatile GLOBAL_AS u32x4_t*)(tile + (unsigned)(g * 1024 + lane * 16));
-  return make_uint4(v.x, v.y, v.z, v.w);
-#else
   return gld16(tile + (unsigned)(g * 1024 + lane * 16));
-#endif
 }
 
 // Kernel arguments are read from the kernarg segment at the point of use.  Left to itself the compiler hoists the ~60
@@ -376,9 +345,6 @@ __device__ __forceinline__ void quad_transpose4(unsigned int (&d)[4][4], unsigne
 
 // store one 32-row tile from the packed words of both n-tiles: w[t][k] = bf16x2(value of register 2k, value of register 2k+1)
 __device__ __forceinline__ void store_tile_packed(GLOBAL_AS void* buf, int F, int s0, int mt, int lane, const unsigned int (&w)[2][8]) {
-#ifdef LAB4D_ABL_L2STORE  // kernel experiment (timing only): every wave keeps writing the same 2048-sample window, so the stores never reach HBM
-  s0 &= 0x7ff;
-#endif
   const int n = lane & 31, h = lane >> 5, q = n & 3, k = n >> 2;
   GLOBAL_AS char* base = (GLOBAL_AS char*)buf + tile_base_offset<PBF16>(F, s0, 32 * mt);
   const unsigned lo = tile_lane_offset<PBF16>(4 * h + q, k);
@@ -393,53 +359,26 @@ __device__ __forceinline__ void store_tile_packed(GLOBAL_AS void* buf, int F, in
     }
   quad_transpose4(d, c);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) gst16o(base, lo + tile_lane_offset<PBF16>(8 * i, 0), c[i][0], c[i][1], c[i][2], c[i][3]);
+  for (int i = 0; i < 4; ++i) gst16(base + (lo + tile_lane_offset<PBF16>(8 * i, 0)), c[i][0], c[i][1], c[i][2], c[i][3]);
 }
 
 
-// ---- tile store through the LDS transpose-read (round 2, second session) ----------------------------------------------------------
-// The packed units of a finished tile sit in the wave's slab anyway ([n-tile][unit][lane] 16 B: 8 features of one sample).  gfx950's
+// ---- tile store through the LDS transpose-read (the weights-stationary kernels of mlp_kernels_ws.hpp) ----------------------------------------
+// The packed units of a finished tile sit in a slab anyway ([n-tile][unit][lane] 16 B: 8 features of one sample).  gfx950's
 // ds_read_b64_tr_b16 is a free 4x4 16-bit transpose with ARBITRARY per-lane chunk addresses (tools/probes/tr_probe.hip, verified on
 // hardware: inside a 16-lane group, lane i's element j is element i&3 of the 8-byte chunk addressed by lane (i>>2) + 4j).  With lane
 // c = (m = c&3, j = c>>2) of group G = (h = G&1, S = G>>1) pointing at sample 32S + 8m + j (and + 4 for a second read), lane i
 // receives samples 32S + 8(i>>2) + 0..7 of ONE feature = exactly a 16-byte piece of the [feature][64 samples] row: 8 reads + 4 stores per
-// 32 x 64 tile and NO VALU work (the DPP network it replaces: 16 v_perm + 32 v_cndmask_dpp per tile).  The reads are issued right
-// after the slab writes and waited for in `flush`, behind the next tile's weight requests.
-// Measured on the shipped one-wave-per-SIMD kernels (-DLAB4D_TRSTORE): parity-green, forward unchanged (6.71 vs 6.74 ms), backward
-// slower (8.42 vs 7.91 ms): with nothing to switch to, 8 more LDS round trips per step cost more than 48 VALU slots save -- so the
-// DPP network stays the default HERE.  The path is kept because it is what makes 32-sample tiles (two waves per SIMD for the
-// 256-wide nets) practical: a 32 x 32 tile needs an 8 x 8 16-bit transpose in registers, but only 4 of these reads.
+// 32 x 64 tile and NO VALU work (the DPP network of store_tile_packed: 16 v_perm + 32 v_cndmask_dpp per tile; the one-wave-per-SIMD
+// kernels keep that network).  The reads are ws_tr_issue / ws_trp_issue; TrTile holds a whole tile's.
 struct TrTile {
   unsigned long long a[4], b[4];  // [2q + a]: first / second read of a pair
 };
-__device__ __forceinline__ unsigned tr_lane_base(unsigned slab_lds, int UW, int lane) {
-  // LDS byte address of this lane's supplier chunk for (mt = 0, q = 0, a = 0, first read)
-  const int i = lane & 15, G = lane >> 4, h = G & 1, S = G >> 1, m = i & 3, j = i >> 2;
-  const int sigma = 32 * S + 8 * m + j, n = sigma >> 1, t = sigma & 1;
-  return slab_lds + (unsigned)(((t * UW) * 64 + 32 * h + n) * 16);
-}
-__device__ __forceinline__ void tr_issue(unsigned addr /* tr_lane_base + mt * 2048 */, TrTile& r) {
-  // second read of a pair: samples + 4 = lane n + 2 = + 32 bytes; q: next unit = + 1024 bytes; a: + 8 bytes
-  asm volatile("ds_read_b64_tr_b16 %0, %8\n\t"
-               "ds_read_b64_tr_b16 %4, %8 offset:32\n\t"
-               "ds_read_b64_tr_b16 %1, %8 offset:8\n\t"
-               "ds_read_b64_tr_b16 %5, %8 offset:40\n\t"
-               "ds_read_b64_tr_b16 %2, %8 offset:1024\n\t"
-               "ds_read_b64_tr_b16 %6, %8 offset:1056\n\t"
-               "ds_read_b64_tr_b16 %3, %8 offset:1032\n\t"
-               "ds_read_b64_tr_b16 %7, %8 offset:1064"
-               : "=&v"(r.a[0]), "=&v"(r.a[1]), "=&v"(r.a[2]), "=&v"(r.a[3]), "=&v"(r.b[0]), "=&v"(r.b[1]), "=&v"(r.b[2]), "=&v"(r.b[3])
-               : "v"(addr)
-               : "memory");
-}
 __device__ __forceinline__ void tr_wait(TrTile& r) {
   asm volatile("s_waitcnt lgkmcnt(0)"
                : "+v"(r.a[0]), "+v"(r.a[1]), "+v"(r.a[2]), "+v"(r.a[3]), "+v"(r.b[0]), "+v"(r.b[1]), "+v"(r.b[2]), "+v"(r.b[3]));
 }
 __device__ __forceinline__ void tr_store(GLOBAL_AS void* buf, int F, int s0, int mt, int lane, const TrTile& r) {
-#ifdef LAB4D_ABL_L2STORE
-  s0 &= 0x7ff;
-#endif
   const int i = lane & 15, G = lane >> 4, h = G & 1, S = G >> 1;
   GLOBAL_AS char* base = (GLOBAL_AS char*)buf + tile_base_offset<PBF16>(F, s0, 32 * mt);
   const unsigned lo = (unsigned)((4 * h + (i & 3)) * 128 + (32 * S + 8 * (i >> 2)) * 2);
@@ -448,31 +387,6 @@ __device__ __forceinline__ void tr_store(GLOBAL_AS void* buf, int F, int s0, int
     const unsigned long long A = r.a[qa], B = r.b[qa];
     gst16(base + (lo + (unsigned)((16 * (qa >> 1) + 8 * (qa & 1)) * 128)), (unsigned)A, (unsigned)(A >> 32), (unsigned)B, (unsigned)(B >> 32));
   }
-}
-
-// The same tile IO in four independent pieces (qa = 2q + a: rows 16q + 8a + ..): two transposing reads, one 16-byte store each.
-// -DLAB4D_TRSPREAD issues the pieces BETWEEN the MFMAs of the second half of the step the tile was finished in, instead of four
-// back-to-back stores per wave at the end of every step (the counters say the vector L1 stalls the store data path for a quarter
-// of the kernel: profiles/r02_stall_counters.txt).  The data waits in the wave's slab, not in registers.
-struct TrPiece {
-  unsigned long long a, b;
-};
-template <int QA>
-__device__ __forceinline__ void trp_issue(unsigned addr /* tr_lane_base + mt * 2048 */, TrPiece& r) {
-  constexpr int OFF = 1024 * (QA >> 1) + 8 * (QA & 1);
-  asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\t"
-               "ds_read_b64_tr_b16 %1, %2 offset:%4"
-               : "=&v"(r.a), "=&v"(r.b)
-               : "v"(addr), "n"(OFF), "n"(OFF + 32)
-               : "memory");
-}
-template <int QA>
-__device__ __forceinline__ void trp_store(GLOBAL_AS void* buf, int F, int s0, int mt, int lane, TrPiece& r) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r.a), "+v"(r.b));
-  const int i = lane & 15, G = lane >> 4, h = G & 1, S = G >> 1;
-  GLOBAL_AS char* base = (GLOBAL_AS char*)buf + tile_base_offset<PBF16>(F, s0, 32 * mt);
-  const unsigned lo = (unsigned)((4 * h + (i & 3)) * 128 + (32 * S + 8 * (i >> 2)) * 2);
-  gst16(base + (lo + (unsigned)((16 * (QA >> 1) + 8 * (QA & 1)) * 128)), (unsigned)r.a, (unsigned)(r.a >> 32), (unsigned)r.b, (unsigned)(r.b >> 32));
 }
 
 template <class P>
@@ -592,104 +506,23 @@ __device__ __forceinline__ void emb_pair(int pair, const float* x /* [6]: point,
 // the end of the step, and after ONE barrier per step all waves read the groups they need back (lane-linear
 // ds_read_b128, conflict-free).  Up to ACACHE_G groups go through LDS (2 buffers x 16 KiB: with the four 32 KiB slabs
 // that is the CU's whole 160 KiB); the few groups beyond (skip-layer embedding columns) keep the direct path.
-#ifndef LAB4D_ACACHE_G
-#define LAB4D_ACACHE_G 14
-#endif
-constexpr int ACACHE_G = LAB4D_ACACHE_G;  // 2 x 14 KiB: leaves 4 KiB of the 160 KiB unallocated (a kernel that needs ALL of the LDS cannot be co-scheduled with anything, e.g. a profiler's helper)
+constexpr int ACACHE_G = 14;  // 2 x 14 KiB: leaves 4 KiB of the 160 KiB unallocated (a kernel that needs ALL of the LDS cannot be co-scheduled with anything, e.g. a profiler's helper)
 // The narrow fg nets (feature 128 wide, visibility 64 wide; bf16) are built for TWO workgroups per CU (two waves per SIMD from independent, not lock-stepped
 // workgroups: while one waits at its barrier / on a store the other issues MFMAs): <= 256 registers per lane
 // (__launch_bounds__(256, 2)) and <= 78 KiB of LDS (4 x 16 KiB slabs + 2 x 7 KiB of shared A groups).
 template <class Net, class P, bool BWD = false>
 constexpr int want_occ() {
-#ifdef LAB4D_ABL_OCC1
-  return 1;
-#else
   // (the affine-form skin nets were tried at 2: their forward spills 126-158 registers at 256, their backward carries 128 accumulators of the table gradient)
   return (P::BF16 && (Net::ID == LAB4D_NET_FEAT || Net::ID == LAB4D_NET_VIS)) ? 2 : 1;  // the bg nets (per-frame bias in two layers) spill 25-53 registers at 256
-#endif
 }
 template <class Net, class P>
 constexpr int acache_g() {
-#ifdef LAB4D_ABL_ACG14
-  return ACACHE_G;
-#elif defined(LAB4D_ABL_ACG7)
-  return (P::BF16 && (Net::ID == LAB4D_NET_FEAT || Net::ID == LAB4D_NET_VIS)) ? 7 : ACACHE_G;
-#else
   return want_occ<Net, P>() == 2 ? 7 : ACACHE_G;
-#endif
 }
 __device__ __forceinline__ void wg_step_barrier() {
   // LDS writes of this wave visible + everybody arrived.  Raw s_barrier: __syncthreads() would also drain the
   // outstanding activation stores (vmcnt(0)), a full HBM round trip per step.
-#ifdef LAB4D_ABL_NOBAR  // kernel experiment (timing only, results wrong): no lock-step
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-}
-
-// ---- LDS-DMA weight stream (round 4, -DLAB4D_ADMA; backward chain, bf16) -------------------------------------------------------------------
-// The shared A groups of a step go global -> LDS directly (global_load_lds_dwordx4: 1 KiB per wave-instruction, lane-linear, no staging registers,
-// no ds_write), issued right behind the step barrier into the buffer the previous step finished reading -- one step of lead instead of two,
-// 16 registers and 4 LDS stores per wave and step less.  Two things make it work with compiler-managed waits: (1) the DMA is the BUILTIN, so the
-// waitcnt pass counts it like any other vector-memory operation (an inline-asm DMA is invisible to it and shifts every counted vmcnt of the step
-// by the number of hidden pieces: each wait then also drains the previous step's tile stores); (2) the two buffers are two separate __shared__
-// arrays selected by compile-time constants, so a read of the buffer that landed a step ago is not ordered behind the DMA that has just been
-// issued into the other one (the pass tracks LDS-DMA destinations per LDS variable).  What the compiler cannot know is the cross-wave part: a
-// wave's pieces must have landed before it arrives at the step barrier (wg_step_barrier_dma: all but the N most recent vector-memory operations --
-// the tile stores issued at the end of the step -- are waited for).
-__device__ __forceinline__ void a_dma_1k(const GLOBAL_AS void* gsrc_lane, __attribute__((address_space(3))) void* lds_base_uniform) {
-#if defined(LAB4D_ADMA) && LAB4D_ADMA == 2  // experiment: the same transfer as inline asm (invisible to the waitcnt pass; M0 is used by nothing else in these kernels)
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc_lane), "s"(__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)lds_base_uniform)) : "memory");
-#else
-  __builtin_amdgcn_global_load_lds((const GLOBAL_AS unsigned int*)gsrc_lane, (__attribute__((address_space(3))) unsigned int*)lds_base_uniform, 16, 0, 0);
-#endif
-}
-template <int KEEP>
-__device__ __forceinline__ void wg_step_barrier_dma() {
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(KEEP) : "memory");
-}
-template <class P>
-constexpr int bwd_step_stores() {  // the dZ tile stores flush_act issues at the very end of a backward step (store_tile_packed: four 16-byte stores)
-#if defined(LAB4D_ABL_NOSTORE) || defined(LAB4D_TRSPREAD) || defined(LAB4D_TRSTORE)
-  return 0;
-#else
-  return P::BF16 ? 4 : 0;
-#endif
-}
-template <class P>
-constexpr bool use_adma() {
-#ifdef LAB4D_ADMA
-  return P::BF16;
-#else
-  return false;
-#endif
-}
-
-// One wave per SIMD issues in order: an MFMA that is followed in the instruction stream by a long run of VALU work leaves the matrix pipe
-// idle for the whole run, and a run of back-to-back MFMAs leaves the VALU idle.  The machine scheduler interleaves the two only
-// partly (tools/isa_blocks.py: runs of 40-100 vector instructions without an MFMA at the end of every pipeline step), so the step
-// regions ask for the pattern explicitly: NM times {1 MFMA, NV VALU}.  Scheduling only -- results are unaffected.
-#ifndef LAB4D_SCHED_NV
-#define LAB4D_SCHED_NV 5
-#endif
-#ifndef LAB4D_SCHED_NV_FWD
-#define LAB4D_SCHED_NV_FWD 5
-#endif
-#ifndef LAB4D_SCHED_FWD_ON  // forward chains: every pattern tried (3..7 VALU per MFMA) made the static schedule WORSE than the scheduler's own; off
-#define LAB4D_SCHED_FWD_ON false
-#endif
-template <class Net>
-constexpr bool sched_il_bwd() { return Net::ID != LAB4D_NET_FG_COLOR; }  // the colour net's backward spills 10 registers with the pattern
-template <int NM, int NV, bool ON = true>
-__device__ __forceinline__ void sched_interleave() {
-#ifdef LAB4D_SCHED_IL
-#pragma unroll
-  for (int i = 0; i < (ON ? NM : 0); ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-    __builtin_amdgcn_sched_group_barrier(0x002, NV, 0);  // VALU
-  }
-#endif
 }
 
 // ---- layer kinds ----------------------------------------------------------------------------------
@@ -833,9 +666,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
   const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   uint4* slab = slab_all + wid * Slab<Net, P>::UNITS_PER_WAVE + lane;  // + (t*UW + u)*64
   const int wave = blockIdx.x * 4 + wid, nwaves = gridDim.x * 4;
-  // LDS byte address of this lane's chunk for the transposing tile store (see tr_issue)
-  const unsigned tr_base = tr_lane_base((unsigned)(size_t)(__attribute__((address_space(3))) uint4*)(slab_all + wid * Slab<Net, P>::UNITS_PER_WAVE), UW, lane);
-  TrTile trt;
 
   // device-side sample count: only the first *S_dev samples exist (stream-compacted evaluation); tiles beyond them are skipped
   int S_eff = a.S, ntiles = a.ntiles;
@@ -1136,22 +966,18 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
       // workgroup-shared A groups (see wg_step_barrier): wave w moves groups w, w+4, ... (clamped: a duplicate fetch of the
       // last group keeps the code branch-free when GL is not a multiple of 4)
       auto a_fetch = [&](int mt, uint4 (&stg)[NQ]) {
-#ifndef LAB4D_ABL_NOAFETCH
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
           const int g = wid + 4 * i < GL ? wid + 4 * i : GL - 1;
           stg[i] = load_a(Wl, G, mt, g, lane);
         }
-#endif
       };
       auto a_stash = [&](int buf, const uint4 (&stg)[NQ]) {
-#ifndef LAB4D_ABL_NOAFETCH
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
           const int g = wid + 4 * i < GL ? wid + 4 * i : GL - 1;
           abuf[(buf * ACG + g) * 64 + lane] = stg[i];
         }
-#endif
       };
       auto a_grab = [&](int buf, uint4 (&A)[G]) {
 #pragma unroll
@@ -1182,9 +1008,7 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) w[t][k] = pack2bf_op(acc[t][2 * k], acc[t][2 * k + 1]);
           if constexpr (ls.relu != 0) {
-#ifndef LAB4D_ABL_NOMASK
             if constexpr (ST) wbits = pk_alive_bits(w);
-#endif
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -1194,9 +1018,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
           for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int q = 0; q < 2; ++q) slab[(t * UW + 2 * mt + q) * 64] = make_uint4(w[t][4 * q], w[t][4 * q + 1], w[t][4 * q + 2], w[t][4 * q + 3]);
-#if defined(LAB4D_TRSTORE) && !defined(LAB4D_ABL_NOSTORE)
-          if constexpr (ST || fwd_any_export<Net>(R)) tr_issue(tr_base + (unsigned)mt * 2048u, trt);  // read back transposed, stored in `flush`
-#endif
           return;
         }
         if constexpr (ls.relu != 0) {
@@ -1210,7 +1031,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
               for (int r = 0; r < 16; ++r)
                 acc[t][r] = __uint_as_float(__float_as_uint(acc[t][r]) & (unsigned int)__builtin_amdgcn_sbfe((int)bits, mask_bit<P>(t, r), 1));
           } else {
-#ifndef LAB4D_ABL_NOMASK
             if constexpr (ST && !LAST) {
               unsigned int bits = 0;
 #pragma unroll
@@ -1219,7 +1039,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
                 for (int r = 0; r < 16; ++r) bits |= (acc[t][r] > 0.f ? 1u : 0u) << mask_bit<P>(t, r);
               maskl[((size_t)tile * MT + mt) * 64 + lane] = bits;
             }
-#endif
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -1235,9 +1054,7 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
             for (int r = 0; r < 16; ++r) acc[t][r] += e[t][r];
         }
         if constexpr (ST) {
-#ifndef LAB4D_ABL_NOSTORE
           if constexpr (!LAST && ACTS) store_tile<P>(actl, 32 * MT, s0, mt, lane, acc);
-#endif
         } else if constexpr (fwd_any_export<Net>(R)) {
           if (actl) store_tile<P>(actl, 32 * MT, s0, mt, lane, acc);  // inference: only the layer another net consumes
         }
@@ -1279,24 +1096,10 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
       auto flush = [&](int mt, const unsigned int (&w)[2][8], unsigned int wbits) {
         if constexpr (PACKED) {
           if constexpr (ST) {
-#ifndef LAB4D_ABL_NOMASK
             if constexpr (ls.relu != 0) maskl[((size_t)tile * MT + mt) * 64 + lane] = wbits;
-#endif
-#ifndef LAB4D_ABL_NOSTORE
-#ifndef LAB4D_TRSTORE
             if constexpr (ACTS) store_tile_packed(actl, 32 * MT, s0, mt, lane, w);
-#else
-            tr_wait(trt);
-            if constexpr (ACTS) tr_store(actl, 32 * MT, s0, mt, lane, trt);
-#endif
-#endif
           } else if constexpr (fwd_any_export<Net>(R)) {
-#ifndef LAB4D_TRSTORE
             if (actl) store_tile_packed(actl, 32 * MT, s0, mt, lane, w);  // inference: only the layer another net consumes
-#else
-            tr_wait(trt);
-            if (actl) tr_store(actl, 32 * MT, s0, mt, lane, trt);
-#endif
           }
         }
       };
@@ -1325,49 +1128,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
       wg_step_barrier();
       a_grab(0, A);
       constexpr int NSTEP = MT - 1, NPAIR = NSTEP / 2;
-#ifdef LAB4D_PROG_FWD  // measured: -3..-6 % on the backward chains, but the forward chains (which also hold the embedding and the bias tile) spill 26-73 registers with it and get 7-10 % slower: backward only
-      // Progressive weight reload.  Step of tile T: the A registers hold tile T; each group is re-read from buffer (T+1)&1
-      // (tile T+1, stashed during the previous step) right behind its MFMAs; the staging registers (tile T+2) go to buffer T&1,
-      // which was last read during the previous step; tile T+3 is requested.  One barrier per step as before: it orders
-      // "everybody has read buffer T&1" before this step's stash and "stash of tile T+1 visible" before this step's reads.
-      mfma_tile(std::bool_constant<(MT > 1)>{}, 1, 1, A, bv, acc0);  // tile 0, reloading tile 1 from buffer 1
-      if constexpr (MT > 1) {
-        wg_step_barrier();  // every wave has grabbed tile 0 out of buffer 0
-        a_stash(0, stg);    // tile 2
-        a_fetch(MT > 3 ? 3 : MT - 1, stg);
-      }
-      if constexpr (NPAIR > 0) {
-#pragma nounroll
-        for (int k = 0; k < 2 * NPAIR; k += 2) {
-          wg_step_barrier();
-          mfma_tile(std::true_type{}, k + 2 < MT ? k + 2 : MT - 1, 0, A, bv, acc1);  // tile k+1, reloading tile k+2 from buffer 0
-          epilogue(k, acc0, pw, pbits);
-          prefetch(k + 1);
-          a_stash(1, stg);  // tile k+3
-          a_fetch(k + 4 < MT ? k + 4 : MT - 1, stg);
-          flush(k, pw, pbits);
-          wg_step_barrier();
-          mfma_tile(std::true_type{}, k + 3 < MT ? k + 3 : MT - 1, 1, A, bv, acc0);  // tile k+2, reloading tile k+3 from buffer 1
-          epilogue(k + 1, acc1, pw, pbits);
-          prefetch(k + 2 < MT ? k + 2 : MT - 1);
-          a_stash(0, stg);  // tile k+4
-          a_fetch(k + 5 < MT ? k + 5 : MT - 1, stg);
-          flush(k + 1, pw, pbits);
-        }
-      }
-      if constexpr (NSTEP % 2 == 1) {
-        wg_step_barrier();
-        mfma_tile(std::false_type{}, 0, -1, A, bv, acc1);  // tile MT-1
-        epilogue(MT - 2, acc0, pw, pbits);
-        flush(MT - 2, pw, pbits);
-        prefetch(MT - 1);
-        epilogue(MT - 1, acc1, pw, pbits);
-        flush(MT - 1, pw, pbits);
-      } else {
-        epilogue(MT - 1, acc0, pw, pbits);
-        flush(MT - 1, pw, pbits);
-      }
-#else
       mfma_tile(std::bool_constant<(MT > 1)>{}, 1, -1, A, bv, acc0);
       if constexpr (NPAIR > 0) {
 #pragma nounroll
@@ -1382,7 +1142,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
           a_stash(0, stg);
           a_fetch(k + 3 < MT ? k + 3 : MT - 1, stg);
           flush(k, pw, pbits);
-          if constexpr (PACKED) sched_interleave<NT * G, LAB4D_SCHED_NV_FWD, LAB4D_SCHED_FWD_ON>();
           // step k+1
           wg_step_barrier();
           a_grab(0, A);
@@ -1392,7 +1151,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
           a_stash(1, stg);
           a_fetch(k + 4 < MT ? k + 4 : MT - 1, stg);
           flush(k + 1, pw, pbits);
-          if constexpr (PACKED) sched_interleave<NT * G, LAB4D_SCHED_NV_FWD, LAB4D_SCHED_FWD_ON>();
         }
       }
       if constexpr (NSTEP % 2 == 1) {
@@ -1401,7 +1159,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
         mfma_tile(std::false_type{}, 0, -1, A, bv, acc1);  // tile MT-1
         epilogue(MT - 2, acc0, pw, pbits);
         flush(MT - 2, pw, pbits);
-        if constexpr (PACKED) sched_interleave<NT * G, LAB4D_SCHED_NV_FWD, LAB4D_SCHED_FWD_ON>();
         prefetch(MT - 1);
         epilogue(MT - 1, acc1, pw, pbits);
         flush(MT - 1, pw, pbits);
@@ -1409,7 +1166,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P>())) k_mlp_fwd(FwdK a) {
         epilogue(MT - 1, acc0, pw, pbits);
         flush(MT - 1, pw, pbits);
       }
-#endif
     });
   }
 }
@@ -1433,7 +1189,7 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P, true>())) k_mlp_bwd(Bwd
   constexpr int NT = P::NT, TILE = P::TILE, NL = Net::NL, UW = Slab<Net, P>::UW;
   constexpr int ACG = acache_g<Net, P>();
   __shared__ uint4 slab_all[4 * Slab<Net, P>::UNITS_PER_WAVE];
-  // workgroup-shared A groups (see wg_step_barrier): two buffers, two LDS variables (the LDS-DMA build relies on the compiler telling them apart)
+  // workgroup-shared A groups (see wg_step_barrier): two buffers, two LDS variables
   __shared__ uint4 abuf0[ACG * 64];
   __shared__ uint4 abuf1[ACG * 64];
 #define LAB4D_ABUF(buf) ((buf) ? abuf1 : abuf0)
@@ -1465,8 +1221,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P, true>())) k_mlp_bwd(Bwd
   uint4* slab = slab_all + wid * Slab<Net, P>::UNITS_PER_WAVE + lane;
   float* stagef = reinterpret_cast<float*>(slab_all + wid * Slab<Net, P>::UNITS_PER_WAVE);  // wave-private staging (raw-input nets)
   const int wave = blockIdx.x * 4 + wid, nwaves = gridDim.x * 4;
-  const unsigned tr_base = tr_lane_base((unsigned)(size_t)(__attribute__((address_space(3))) uint4*)(slab_all + wid * Slab<Net, P>::UNITS_PER_WAVE), UW, lane);
-  TrTile trt;
 
   for (int tile = wave; tile < a.ntiles; tile += nwaves) {
     const int s0 = tile * TILE;
@@ -1561,8 +1315,7 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P, true>())) k_mlp_bwd(Bwd
         for (int u = 0; u < GK; ++u) bin[t][u] = slab[(t * UW + u) * 64];
 
       // MFMA phase of one row tile of W^T: acc = W^T[mt] dz.  pre = row tile whose A groups are requested behind it.
-      auto no_hook = [&](auto) {};
-      auto mfma_tile = [&](auto has_pre, int pre, int rbuf, uint4 (&A)[GK], f32x16_t (&acc)[NT], auto&& hook) {
+      auto mfma_tile = [&](auto has_pre, int pre, int rbuf, uint4 (&A)[GK], f32x16_t (&acc)[NT]) {
         constexpr bool PRE = decltype(has_pre)::value;
 #pragma unroll
         for (int t = 0; t < NT; ++t)
@@ -1574,83 +1327,59 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P, true>())) k_mlp_bwd(Bwd
           for (int t = 0; t < NT; ++t) mma_unit<P>(acc[t], A[g], bin[t][g]);
           if constexpr (PRE) {
             if (g >= GL) A[g] = load_a(Wt, GK, pre, g, lane);  // groups beyond the LDS-shared ones
-            else if (rbuf >= 0) A[g] = LAB4D_ABUF(rbuf)[g * 64 + lane];  // progressive reload (see the forward kernel)
+            else if (rbuf >= 0) A[g] = LAB4D_ABUF(rbuf)[g * 64 + lane];  // progressive reload (see pipeline)
           }
-          hook(gc);
         });
       };
       auto a_fetch = [&](int mt, uint4 (&stg)[NQ]) {
-#ifndef LAB4D_ABL_NOAFETCH
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
           const int g = wid + 4 * i < GL ? wid + 4 * i : GL - 1;
           stg[i] = load_a(Wt, GK, mt, g, lane);
         }
-#endif
       };
       auto a_stash = [&](int buf, const uint4 (&stg)[NQ]) {
-#ifndef LAB4D_ABL_NOAFETCH
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
           const int g = wid + 4 * i < GL ? wid + 4 * i : GL - 1;
           LAB4D_ABUF(buf)[g * 64 + lane] = stg[i];
         }
-#endif
       };
       auto a_grab = [&](int buf, uint4 (&A)[GK]) {
 #pragma unroll
         for (int g = 0; g < GL; ++g) A[g] = LAB4D_ABUF(buf)[g * 64 + lane];
       };
-      auto a_dma = [&](int mt, int buf) {  // this wave's quarter of row tile mt's shared groups -> LDS buffer `buf` (see a_dma_1k)
-        const GLOBAL_AS char* tile = (const GLOBAL_AS char*)Wt + (size_t)(unsigned)(mt * GK) * 1024u;
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) {
-          const int g = wid + 4 * i < GL ? wid + 4 * i : GL - 1;
-          a_dma_1k(tile + (unsigned)(g * 1024 + lane * 16), (__attribute__((address_space(3))) void*)(LAB4D_ABUF(buf) + g * 64));
-        }
-      };
       // Software pipeline over N row tiles starting at tile0 (same scheme as the forward chain): step k issues the MFMAs
       // of tile k+1 into the other accumulator set in the same basic block as the epilogue of tile k.
       // pre(j) requests the HBM inputs of epi(j) (mask bits, stored embedding / external gradient tile) one step ahead.
-      auto pipeline = [&](auto n_c, int tile0, auto&& pre, auto&& epi, auto&& fl, auto&& prem, auto&& sp, auto&& sp_all, auto nst_c) {
+      // Progressive weight reload.  Step of tile T: the A registers hold tile T; each group is re-read from buffer (T+1)&1
+      // (tile T+1, stashed during the previous step) right behind its MFMAs; the staging registers (tile T+2) go to buffer T&1,
+      // which was last read during the previous step; tile T+3 is requested.  One barrier per step: it orders
+      // "everybody has read buffer T&1" before this step's stash and "stash of tile T+1 visible" before this step's reads.
+      auto pipeline = [&](auto n_c, int tile0, auto&& pre, auto&& epi, auto&& fl, auto&& prem) {
         constexpr int N = decltype(n_c)::value;
-        // LDS-DMA weight stream: NST = vector-memory operations a step issues LAST, unconditionally (the 4 dZ tile stores of flush_act; 0 for the
-        // embedding pipeline, whose epilogue stores nothing): the per-step wait leaves exactly those in flight
-        constexpr bool ADMA = use_adma<P>();
-        constexpr int NST = decltype(nst_c)::value;
         if constexpr (N > 0) {
           uint4 A[GK], stg[NQ];
           f32x16_t acc0[NT], acc1[NT];
           unsigned int pw[2][8];  // packed tile waiting for its store (see the forward kernel: weight loads first, stores last)
           wg_step_barrier();  // nobody still reads the buffers for the previous pipeline
-          if constexpr (ADMA) {
-            a_dma(tile0, 0);
-            if constexpr (N > 1) a_dma(tile0 + 1, 1);
-          } else {
-            a_fetch(tile0, stg);
-            a_stash(0, stg);
-            if constexpr (N > 1) {
-              a_fetch(tile0 + 1, stg);
-              a_stash(1, stg);
-            }
-            a_fetch(tile0 + (N > 2 ? 2 : N - 1), stg);
+          a_fetch(tile0, stg);
+          a_stash(0, stg);
+          if constexpr (N > 1) {
+            a_fetch(tile0 + 1, stg);
+            a_stash(1, stg);
           }
+          a_fetch(tile0 + (N > 2 ? 2 : N - 1), stg);
 #pragma unroll
           for (int g = GL; g < GK; ++g) A[g] = load_a(Wt, GK, tile0, g, lane);
           pre(0);
           prem(std::integral_constant<int, 0>{}, 0);  // ReLU sign words: requested TWO steps ahead (see pre_mask)
           prem(std::integral_constant<int, 1>{}, N > 1 ? 1 : 0);
-          if constexpr (ADMA) wg_step_barrier_dma<0>();  // once per pipeline: both buffers landed (this also drains the previous layer's last stores)
-          else wg_step_barrier();
+          wg_step_barrier();
           a_grab(0, A);
           constexpr int NSTEP = N - 1, NPAIR = NSTEP / 2;
-#ifndef LAB4D_ABL_NOPROG
-          if constexpr (ADMA && N > 1) {
-            wg_step_barrier();                      // every wave has grabbed tile 0 out of buffer 0 ...
-            a_dma(tile0 + (N > 2 ? 2 : N - 1), 0);  // ... so tile 2 is requested into it BEFORE tile 0's matrix work: a whole step of lead
-          }
-          mfma_tile(std::bool_constant<(N > 1)>{}, tile0 + 1, 1, A, acc0, no_hook);  // tile 0, reloading tile 1 from buffer 1
-          if constexpr (N > 1 && !ADMA) {
+          mfma_tile(std::bool_constant<(N > 1)>{}, tile0 + 1, 1, A, acc0);  // tile 0, reloading tile 1 from buffer 1
+          if constexpr (N > 1) {
             wg_step_barrier();  // every wave has grabbed tile 0 out of buffer 0
             a_stash(0, stg);    // tile 2
             a_fetch(tile0 + (N > 3 ? 3 : N - 1), stg);
@@ -1658,106 +1387,27 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P, true>())) k_mlp_bwd(Bwd
           if constexpr (NPAIR > 0) {
 #pragma nounroll
             for (int k = 0; k < 2 * NPAIR; k += 2) {
-              if constexpr (ADMA) {
-                // step of tile k+1: its reload source (tile k+2 in buffer 0) was requested one step ago by every wave -> landed before anyone passes;
-                // buffer 1 (tile k+1) was read out during the previous step -> tile k+3 goes there now
-                if (k == 0) wg_step_barrier_dma<0>(); else wg_step_barrier_dma<NST>();
-                a_dma(tile0 + (k + 3 < N ? k + 3 : N - 1), 1);
-                mfma_tile(std::true_type{}, tile0 + (k + 2 < N ? k + 2 : N - 1), 0, A, acc1, no_hook);
-                epi(k, acc0, pw);
-                pre(k + 1);
-                prem(std::integral_constant<int, 0>{}, k + 2 < N ? k + 2 : N - 1);
-                fl(k, pw);
-                if constexpr (P::BF16) sched_interleave<NT * GK, LAB4D_SCHED_NV, sched_il_bwd<Net>()>();
-                wg_step_barrier_dma<NST>();
-                a_dma(tile0 + (k + 4 < N ? k + 4 : N - 1), 0);
-                mfma_tile(std::true_type{}, tile0 + (k + 3 < N ? k + 3 : N - 1), 1, A, acc0, no_hook);
-                epi(k + 1, acc1, pw);
-                pre(k + 2 < N ? k + 2 : N - 1);
-                prem(std::integral_constant<int, 1>{}, k + 3 < N ? k + 3 : N - 1);
-                fl(k + 1, pw);
-                if constexpr (P::BF16) sched_interleave<NT * GK, LAB4D_SCHED_NV, sched_il_bwd<Net>()>();
-                continue;
-              }
               wg_step_barrier();
-#ifdef LAB4D_TRSPREAD  // the epilogue first in program order: its slab writes precede the transposing reads of the hook
+              mfma_tile(std::true_type{}, tile0 + (k + 2 < N ? k + 2 : N - 1), 0, A, acc1);  // tile k+1, reloading tile k+2 from buffer 0
               epi(k, acc0, pw);
-              mfma_tile(std::true_type{}, tile0 + (k + 2 < N ? k + 2 : N - 1), 0, A, acc1, [&](auto gc) { sp(k, gc); });
-#else
-              mfma_tile(std::true_type{}, tile0 + (k + 2 < N ? k + 2 : N - 1), 0, A, acc1, no_hook);
-              epi(k, acc0, pw);
-#endif
               pre(k + 1);
               prem(std::integral_constant<int, 0>{}, k + 2 < N ? k + 2 : N - 1);
-              a_stash(1, stg);
+              a_stash(1, stg);  // tile k+3
               a_fetch(tile0 + (k + 4 < N ? k + 4 : N - 1), stg);
               fl(k, pw);
-              if constexpr (P::BF16) sched_interleave<NT * GK, LAB4D_SCHED_NV, sched_il_bwd<Net>()>();
               wg_step_barrier();
-#ifdef LAB4D_TRSPREAD
+              mfma_tile(std::true_type{}, tile0 + (k + 3 < N ? k + 3 : N - 1), 1, A, acc0);  // tile k+2, reloading tile k+3 from buffer 1
               epi(k + 1, acc1, pw);
-              mfma_tile(std::true_type{}, tile0 + (k + 3 < N ? k + 3 : N - 1), 1, A, acc0, [&](auto gc) { sp(k + 1, gc); });
-#else
-              mfma_tile(std::true_type{}, tile0 + (k + 3 < N ? k + 3 : N - 1), 1, A, acc0, no_hook);
-              epi(k + 1, acc1, pw);
-#endif
               pre(k + 2 < N ? k + 2 : N - 1);
               prem(std::integral_constant<int, 1>{}, k + 3 < N ? k + 3 : N - 1);
-              a_stash(0, stg);
+              a_stash(0, stg);  // tile k+4
               a_fetch(tile0 + (k + 5 < N ? k + 5 : N - 1), stg);
-              fl(k + 1, pw);
-              if constexpr (P::BF16) sched_interleave<NT * GK, LAB4D_SCHED_NV, sched_il_bwd<Net>()>();
-            }
-          }
-          if constexpr (NSTEP % 2 == 1) {
-            if constexpr (ADMA) {
-              if constexpr (NPAIR == 0) wg_step_barrier_dma<0>(); else wg_step_barrier_dma<NST>();  // (the last reload already happened: only the lock-step matters)
-            } else wg_step_barrier();
-#ifdef LAB4D_TRSPREAD
-            epi(N - 2, acc0, pw);
-            mfma_tile(std::false_type{}, 0, -1, A, acc1, [&](auto gc) { sp(N - 2, gc); });
-#else
-            mfma_tile(std::false_type{}, 0, -1, A, acc1, no_hook);
-            epi(N - 2, acc0, pw);
-#endif
-            fl(N - 2, pw);
-            if constexpr (P::BF16) sched_interleave<NT * GK, LAB4D_SCHED_NV, sched_il_bwd<Net>()>();
-            pre(N - 1);
-            epi(N - 1, acc1, pw);
-            fl(N - 1, pw);
-            sp_all(N - 1);  // no matrix work left in this layer to hide the last tile's pieces behind
-          } else {
-            epi(N - 1, acc0, pw);
-            fl(N - 1, pw);
-            sp_all(N - 1);
-          }
-#else
-          mfma_tile(std::bool_constant<(N > 1)>{}, tile0 + 1, -1, A, acc0, no_hook);
-          if constexpr (NPAIR > 0) {
-#pragma nounroll
-            for (int k = 0; k < 2 * NPAIR; k += 2) {
-              wg_step_barrier();
-              a_grab(1, A);
-              mfma_tile(std::true_type{}, tile0 + (k + 2 < N ? k + 2 : N - 1), -1, A, acc1, no_hook);
-              epi(k, acc0, pw);
-              pre(k + 1);
-              a_stash(0, stg);
-              a_fetch(tile0 + (k + 3 < N ? k + 3 : N - 1), stg);
-              fl(k, pw);
-              wg_step_barrier();
-              a_grab(0, A);
-              mfma_tile(std::true_type{}, tile0 + (k + 3 < N ? k + 3 : N - 1), -1, A, acc0, no_hook);
-              epi(k + 1, acc1, pw);
-              pre(k + 2 < N ? k + 2 : N - 1);
-              a_stash(1, stg);
-              a_fetch(tile0 + (k + 4 < N ? k + 4 : N - 1), stg);
               fl(k + 1, pw);
             }
           }
           if constexpr (NSTEP % 2 == 1) {
             wg_step_barrier();
-            a_grab(1, A);
-            mfma_tile(std::false_type{}, 0, -1, A, acc1, no_hook);
+            mfma_tile(std::false_type{}, 0, -1, A, acc1);  // tile N-1
             epi(N - 2, acc0, pw);
             fl(N - 2, pw);
             pre(N - 1);
@@ -1767,38 +1417,25 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P, true>())) k_mlp_bwd(Bwd
             epi(N - 1, acc0, pw);
             fl(N - 1, pw);
           }
-#endif
         }
       };
-      uint4 raw[4];            // prefetched tile: stored embedding (epi_emb) or external gradient (epi_act)
-      unsigned int mbits = 0;  // prefetched ReLU sign bits
+      uint4 raw[4];  // prefetched tile: stored embedding (epi_emb) or external gradient (epi_act)
       // The sign words come from HBM (written by the forward pass a whole chunk earlier).  Requested one step ahead (~0.4 us of
       // matrix work) they arrived later than the epilogue that needs them; they are requested TWO steps ahead into a two-deep ring
       // (even / odd tile, one more register): basefield backward -3.5 %, colour -5 %, feature -6 %, skin -7 % (a build with the
-      // mask work removed altogether bounds the gain at -9 .. -19 %).  -DLAB4D_ABL_MASK1 restores the one-step form.
+      // mask work removed altogether bounds the gain at -9 .. -19 %).
       unsigned int mb0 = 0, mb1 = 0;
-#if !defined(LAB4D_ABL_MASK1) && !defined(LAB4D_ABL_NOPROG)
-#define LAB4D_MASK_RING 1
-#endif
-#if (defined(LAB4D_MASK_RING) || defined(LAB4D_TRSPREAD)) && defined(LAB4D_ABL_NOPROG)
-#error "LAB4D_MASK_RING / LAB4D_TRSPREAD are wired into the progressive-reload pipeline only"
-#endif
       auto no_prem = [&](auto, int) {};
       auto pre_mask = [&](auto par_c, int j) {
-#ifdef LAB4D_MASK_RING
         if constexpr (lp.relu != 0) {
           const unsigned int v = maskp[((size_t)tile * (pad32(lp.mout) / 32) + j) * 64 + lane];
           if constexpr (decltype(par_c)::value == 0) mb0 = v; else mb1 = v;
         }
-#endif
       };
       auto pre_emb = [&](int mt) {
         if constexpr (Net::EMB != 1) load_tile_raw<P>((const GLOBAL_AS void*)a.emb, Net::KE, s0, mt, lane, raw);
       };
       auto pre_act = [&](int j) {
-#ifndef LAB4D_MASK_RING
-        if constexpr (lp.relu != 0) mbits = maskp[((size_t)tile * (pad32(lp.mout) / 32) + j) * 64 + lane];
-#endif
         if constexpr (lp.ext_grad != 0) load_tile_raw<P>((const GLOBAL_AS void*)a.ext_gin, pad32(lp.mout), s0, j, lane, raw);
       };
       // (a) gradient wrt the embedding slots -> input gradient
@@ -1890,11 +1527,7 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P, true>())) k_mlp_bwd(Bwd
       };
       // (b) gradient wrt the previous layer's output -> masked dZ_{l-1}
       auto epi_act = [&](int j, f32x16_t (&acc)[NT], unsigned int (&w)[2][8]) {
-#ifdef LAB4D_MASK_RING
         const unsigned int bits = (j & 1) ? mb1 : mb0;
-#else
-        const unsigned int bits = mbits;
-#endif
         if constexpr (P::BF16) {
 #pragma unroll
           for (int t = 0; t < NT; ++t) acc_fence_if<(want_occ<Net, P, true>() == 2)>(acc[t]);  // the packed path converts with inline asm
@@ -1917,7 +1550,6 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P, true>())) k_mlp_bwd(Bwd
           for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int k = 0; k < 8; ++k) w[t][k] = pack2bf_op(acc[t][2 * k], acc[t][2 * k + 1]);
-#ifndef LAB4D_ABL_NOMASK
           {
             unsigned int alive = lp.relu != 0 ? bits : 0xffffffffu;
 #pragma unroll
@@ -1928,14 +1560,10 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P, true>())) k_mlp_bwd(Bwd
 #pragma unroll
               for (int k = 0; k < 8; ++k) w[t][k] = pk_mask_bf16(w[t][k], pk_m01(alive, t, k));
           }
-#endif
 #pragma unroll
           for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int q = 0; q < 2; ++q) slab[(t * UW + 2 * j + q) * 64] = make_uint4(w[t][4 * q], w[t][4 * q + 1], w[t][4 * q + 2], w[t][4 * q + 3]);
-#if defined(LAB4D_TRSTORE) && !defined(LAB4D_TRSPREAD) && !defined(LAB4D_ABL_NOSTORE)
-          tr_issue(tr_base + (unsigned)j * 2048u, trt);
-#endif
         } else {
           // fp32 tiles: ReLU mask and the zero of the padded tail samples in one AND per value (v_bfe_i32 + v_and)
           unsigned int keep = lp.relu != 0 ? bits : 0xffffffffu;
@@ -1958,64 +1586,18 @@ __global__ void __launch_bounds__(256, (want_occ<Net, P, true>())) k_mlp_bwd(Bwd
         }
       };
       auto flush_act = [&](int j, const unsigned int (&w)[2][8]) {
-        if constexpr (P::BF16) {
-#if !defined(LAB4D_ABL_NOSTORE) && !defined(LAB4D_TRSPREAD)
-#ifndef LAB4D_TRSTORE
-          if constexpr (DZ) store_tile_packed(dzp, pad32(lp.mout), s0, j, lane, w);
-#else
-          tr_wait(trt);
-          tr_store(dzp, pad32(lp.mout), s0, j, lane, trt);
-#endif
-#endif
-        }
-      };
-      // LAB4D_TRSPREAD: the dZ tile j (packed, in the slab since epi_act) leaves in four pieces between the MFMAs of the second half
-      // of the step: piece qa is read at group I(qa) and stored at St(qa) = I(qa) + D; two piece buffers alternate
-      TrPiece tp0, tp1;
-      auto sp_none = [&](int, auto) {};
-      auto sp_all_none = [&](int) {};
-      auto sp_act = [&](int j, auto gc) {
-#if defined(LAB4D_TRSPREAD) && !defined(LAB4D_ABL_NOSTORE)
-        if constexpr (P::BF16) {
-          constexpr int g = decltype(gc)::value;
-          constexpr int D = GK >= 16 ? GK / 8 : 1;
-          if constexpr (GK >= 8) {
-            sfor<0, 4>([&](auto qc) {
-              constexpr int qa = decltype(qc)::value;
-              if constexpr (g == GK - 1 - D * (3 - qa)) trp_store<qa>(dzp, pad32(lp.mout), s0, j, lane, (qa & 1) ? tp1 : tp0);
-            });
-            sfor<0, 4>([&](auto qc) {
-              constexpr int qa = decltype(qc)::value;
-              if constexpr (g == GK - 1 - D * (3 - qa) - D) trp_issue<qa>(tr_base + (unsigned)j * 2048u, (qa & 1) ? tp1 : tp0);
-            });
-          } else if constexpr (g == GK - 1) {  // narrow layers: too few groups to spread over
-            tr_issue(tr_base + (unsigned)j * 2048u, trt);
-            tr_wait(trt);
-            tr_store(dzp, pad32(lp.mout), s0, j, lane, trt);
-          }
-        }
-#endif
-      };
-      auto sp_all_act = [&](int j) {
-#if defined(LAB4D_TRSPREAD) && !defined(LAB4D_ABL_NOSTORE)
-        if constexpr (P::BF16) {
-          tr_issue(tr_base + (unsigned)j * 2048u, trt);
-          tr_wait(trt);
-          tr_store(dzp, pad32(lp.mout), s0, j, lane, trt);
-        }
-#endif
+        if constexpr (P::BF16 && DZ) store_tile_packed(dzp, pad32(lp.mout), s0, j, lane, w);
       };
       // embedding row tiles come first in W^T; they are skipped when no input gradient is wanted
       if constexpr (MTE > 0) {
         if (a.d_x != nullptr) {
-          pipeline(std::integral_constant<int, MTE>{}, 0, pre_emb, epi_emb, no_flush, no_prem, sp_none, sp_all_none, std::integral_constant<int, 0>{});
+          pipeline(std::integral_constant<int, MTE>{}, 0, pre_emb, epi_emb, no_flush, no_prem);
           // raw-input nets: the (TILE, CIN) input-gradient tile sits in the wave's staging area (the slab is idle while the
           // last layer's embedding tiles are processed); one contiguous coalesced copy, rows >= S dropped
           if constexpr (Net::EMB == 1) stage_out(stagef, a.d_x, (long)s0 * Net::CIN, TILE * Net::CIN, (long)a.S * Net::CIN - 1, lane);
         }
       }
-      if constexpr (DO_ACT) pipeline(std::integral_constant<int, MTA>{}, MTE, pre_act, epi_act, flush_act, pre_mask, sp_act, sp_all_act,
-                                     std::integral_constant<int, (DZ ? bwd_step_stores<P>() : 0)>{});
+      if constexpr (DO_ACT) pipeline(std::integral_constant<int, MTA>{}, MTE, pre_act, epi_act, flush_act, pre_mask);
     });
 
     if constexpr (Net::EMB != 1) {
@@ -2080,7 +1662,6 @@ inline int mlp_grid(int ntiles) {
   } while (0)
 
 }  // namespace lab4d
-#include "mlp_kernels_h.hpp"
 #include "mlp_kernels_ws.hpp"
 namespace lab4d {
 // the point-gradient-only modes (forward: masks + embedding only; backward: no dZ) are instantiated for the sdf basefields: the eval path's normals
@@ -2124,15 +1705,6 @@ inline bool launch_ws_fwd(const FwdK& k0, hipStream_t st) {
     return false;
   }
 }
-// LAB4D_BWD_H=1 routes the 256-wide posenc nets to the 8-wave / 32-sample backward chain (mlp_kernels_h.hpp): parity-green but
-// measured SLOWER than the 4-wave kernel (9.12 vs 7.93 ms per 4.2 M samples), so it is off by default
-template <class Net>
-constexpr bool use_bwd_h() { return Net::EMB == 0 && net_wmax<Net>() == 256; }
-inline bool bwd_h_enabled() {
-  static const int on = getenv("LAB4D_BWD_H") ? atoi(getenv("LAB4D_BWD_H")) : 0;
-  return on != 0;
-}
-
 
 #define LAB4D_MLP_INSTANTIATE(Net)                                                                                        \
   namespace lab4d {                                                                                                       \
@@ -2164,12 +1736,6 @@ inline bool bwd_h_enabled() {
     if (precision == LAB4D_PREC_BF16) {                                                                                   \
       if (launch_ws_bwd<Net>(k, st)) return check_launch("mlp_backward");                                                 \
       k.ntiles = k.S_pad / PBF16::TILE; /* padded tail tiles are processed too: they zero-fill dz */                                                                                  \
-      if constexpr (use_bwd_h<Net>()) {                                                                                   \
-        if (bwd_h_enabled()) {                                                                                            \
-          hipLaunchKernelGGL((k_mlp_bwd_h<Net>), dim3(mlp_grid_h(k.S_pad / 32)), dim3(512), 0, st, k);                    \
-          return check_launch("mlp_backward");                                                                            \
-        }                                                                                                                 \
-      }                                                                                                                   \
       if constexpr (Net::EMB == 2) {                                                                                      \
         if (k.spf % PBF16::TILE) LAB4D_MLP_LAUNCH((k_mlp_bwd<Net, PBF16, false>), k, st);                                 \
         else LAB4D_MLP_LAUNCH((k_mlp_bwd<Net, PBF16, true>), k, st);                                                      \

@@ -22,8 +22,7 @@
 // and point-gradient-only modes.
 // Measured (profiles/r04_ws_*.json, r04_clock_under_load.json): -25 % / -17 % shader cycles against the wave-resident forward /
 // backward, -10 % time -- these kernels hold the package at its power cap and the denser one is clocked lower.
-// Build switches: -DLAB4D_WS_TRACE (per-wave cycle trace, outputs wrong), -DLAB4D_WSABL_{NOFLUSH,NOST,NOTR,NOAPF,NOBIAS,NOPOSENC,HALFB} and -DLAB4D_ABL_L2STORE
-// (timing-only ablations, results wrong), -DLAB4D_WS_LINEAR_STORE (lane-linear stores through ds_bpermute: correct, slower), -DLAB4D_WS_BD=n (B ring depth).
+// Build switch: -DLAB4D_WSABL_NOST (timing-only ablation, results wrong: the tile stores are read and waited for but not issued).
 #pragma once
 #include "mlp_kernels.hpp"
 
@@ -86,10 +85,7 @@ __device__ __forceinline__ int ws_mt_rt(int l) {
 }
 
 constexpr int WS_TILE = 128;       // samples per workgroup tile
-#ifndef LAB4D_WS_BD
-#define LAB4D_WS_BD 2
-#endif
-constexpr int WS_BD = LAB4D_WS_BD;  // depth (k-groups) of the B-operand ring between LDS and the MFMAs (2 / 4 / 8 measured: the same time; 2 keeps the colour net free of spills)
+constexpr int WS_BD = 2;  // depth (k-groups) of the B-operand ring between LDS and the MFMAs (2 / 4 / 8 measured: the same time; 2 keeps the colour net free of spills)
 constexpr int WS_BUF = 4 * 16 * 64;  // uint4 slots of one activation buffer: [n-tile 4][unit 16][lane 64] = 64 KiB
 
 // this wave's work items of a layer with MT row tiles: an item = (row tile mt, 64-sample block b).  2 MT items over 8 waves:
@@ -127,17 +123,14 @@ __device__ __forceinline__ void mma_b(f32x16_t& acc, const uint4& a, const u32x4
 
 // One quarter of a finished 32 x 64 tile on its way to HBM (rows 16 q + 8 a + .., qa = 2 q + a; 8 rows x 128 B = 1 KiB), in three stages placed
 // BETWEEN the MFMAs of the layer that follows:
-//   issue: two transposing LDS reads (see tr_issue): lane i of 16-lane group (h, S) then holds samples 32 S + 8 (i >> 2) .. + 7 of row 4 h + (i & 3);
-//   perm (-DLAB4D_WS_LINEAR_STORE only): four ds_bpermute_b32 make the piece LANE-LINEAR (lane L holds bytes 16 L .. 16 L + 15 of the 1 KiB).
-//          Straight out of the transposing reads the four lanes of a quad hold four different rows, and in isolation such a store costs the CU's
-//          address path ~1.4x the cycles of a lane-linear one (tools/probes/store_pattern.hip: 47 vs 34 cycles per store beside MFMAs, 4.8 vs
-//          5.5 TB/s); in the real kernels the four permutes cost 0.4 ms per 4.2 M samples and the linear stores save < 0.1 ms: off;
+//   issue: two transposing LDS reads (see ws_tr_issue): lane i of 16-lane group (h, S) then holds samples 32 S + 8 (i >> 2) .. + 7 of row 4 h + (i & 3);
+//   perm: the wait for the two reads; the piece keeps their lane order (ws_trp_store addresses it accordingly);
 //   store: one global_store_dwordx4 per lane.
 // Why spread at all: a CU writes 64 KiB per layer; issued as one burst at the top of the layer the stores block every wave's memory issue while
 // the matrix pipe idles (measured: 6.4 ms per 4.2 M samples with the burst, 4.2 ms with the stores removed).
 struct WsPiece {
   unsigned long long a, b;  // transposing reads
-  unsigned int d[4];        // lane-linear dwords
+  unsigned int d[4];        // the same dwords, handed to the store
 };
 // ---- slot swizzle of the activation slabs (round 6) ------------------------------------------------------------------------------------------
 // A unit is 64 x 16 B, slot = lane = 32 h + n.  The transposing reads that take a finished tile out (ds_read_b64_tr_b16: two 32-lane groups, bank =
@@ -148,20 +141,16 @@ struct WsPiece {
 // (the t pair is left: both read the same 8-byte half of slots 16 KiB apart; separating them would need 8-byte interleaving, which the 16-byte B
 // operands of the MFMAs cannot have).  The B reads (lane-linear ds_read_b128: 16-lane groups that never mix the two h) and the unit writes
 // (ds_write_b128: aligned 8-lane groups) see a permutation inside their own groups: still conflict-free.  The second read of a pair (samples + 4 =
-// slot n + 2) is `^ 32` on the byte address in both halves.  -DLAB4D_WS_SWZ=0 restores the plain layout (A/B measurements); results are
-// bit-identical either way (tests/test_gpu_mlp_ws.py).
-#ifndef LAB4D_WS_SWZ
-#define LAB4D_WS_SWZ 1
-#endif
-constexpr bool WS_SWZ = LAB4D_WS_SWZ != 0;
-__device__ __forceinline__ int ws_slot(int lane) { return WS_SWZ ? (lane ^ ((lane >> 5) << 1)) : lane; }
-// per-lane part of the transposing tile reads (tr_lane_base of mlp_kernels.hpp with the swizzle): first read of a pair; the second is ^ 32
+// slot n + 2) is `^ 32` on the byte address in both halves.  Results are bit-identical to the plain layout (tests/test_gpu_mlp_ws.py).
+__device__ __forceinline__ int ws_slot(int lane) { return lane ^ ((lane >> 5) << 1); }
+// per-lane part of the transposing tile reads, with the swizzle: first read of a pair; the second is ^ 32.  Lane c = (m = c & 3, j = c >> 2) of
+// group G = (h = G & 1, S = G >> 1) points at sample 32 S + 8 m + j (slot n = sigma >> 1 of n-tile t = sigma & 1)
 __device__ __forceinline__ unsigned ws_tr_lane(int lane) {
   const int i = lane & 15, G = lane >> 4, h = G & 1, S = G >> 1, m = i & 3, j = i >> 2;
   const int sigma = 32 * S + 8 * m + j, n = sigma >> 1, t = sigma & 1;
-  return (unsigned)(((t * 16) * 64 + 32 * h + (WS_SWZ ? (n ^ (2 * h)) : n)) * 16);
+  return (unsigned)(((t * 16) * 64 + 32 * h + (n ^ (2 * h))) * 16);
 }
-// the whole-tile burst (tr_issue of mlp_kernels.hpp) with the pair's second address
+// the whole tile at once (8 reads: q = next unit, + 1024 bytes; a = + 8 bytes), with the pair's second address
 __device__ __forceinline__ void ws_tr_issue(unsigned addr, unsigned addr2, TrTile& r) {
   asm volatile("ds_read_b64_tr_b16 %0, %8\n\t"
                "ds_read_b64_tr_b16 %4, %9\n\t"
@@ -178,36 +167,17 @@ __device__ __forceinline__ void ws_tr_issue(unsigned addr, unsigned addr2, TrTil
 template <int QA>
 __device__ __forceinline__ void ws_trp_issue(unsigned addr /* tile base + lane part */, unsigned addr2 /* tile base + (lane part ^ 32) */, WsPiece& r) {
   constexpr int OFF = 1024 * (QA >> 1) + 8 * (QA & 1);
-#ifdef LAB4D_WSABL_NOTR  // timing experiment (results wrong): no transposing reads, the stores write whatever the registers hold
-  r.a = addr; r.b = addr2 + OFF;
-  return;
-#endif
   asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\t"
                "ds_read_b64_tr_b16 %1, %3 offset:%4"
                : "=&v"(r.a), "=&v"(r.b)
                : "v"(addr), "v"(addr2), "n"(OFF));
 }
-// byte address (lane * 4) of the lane whose transposed piece lane L wants: L = 8 row + piece16  <-  group (h = row >> 2, S = piece16 >> 2), lane (row & 3) + 4 (piece16 & 3)
-__device__ __forceinline__ unsigned ws_perm_addr(int lane) {
-  const int row = lane >> 3, pc = lane & 7;
-  return (unsigned)(4 * (16 * ((row >> 2) + 2 * (pc >> 2)) + (row & 3) + 4 * (pc & 3)));
-}
 // N = LDS operations this wave has certainly issued behind the stage's inputs (a lower bound keeps the wait safe)
 template <int N>
-__device__ __forceinline__ void ws_trp_perm(unsigned perm_addr, WsPiece& r) {
+__device__ __forceinline__ void ws_trp_perm(WsPiece& r) {
   static_assert(N >= 0 && N <= 15, "lgkmcnt field");
   asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(r.a), "+v"(r.b) : "n"(N));
-  const unsigned a0 = (unsigned)r.a, a1 = (unsigned)(r.a >> 32), b0 = (unsigned)r.b, b1 = (unsigned)(r.b >> 32);
-#ifndef LAB4D_WS_LINEAR_STORE
-  r.d[0] = a0; r.d[1] = a1; r.d[2] = b0; r.d[3] = b1;  // the piece keeps the lane order of the transposing reads (ws_trp_store addresses it accordingly)
-  return;
-#endif
-  asm volatile("ds_bpermute_b32 %0, %4, %5\n\t"
-               "ds_bpermute_b32 %1, %4, %6\n\t"
-               "ds_bpermute_b32 %2, %4, %7\n\t"
-               "ds_bpermute_b32 %3, %4, %8"
-               : "=&v"(r.d[0]), "=&v"(r.d[1]), "=&v"(r.d[2]), "=&v"(r.d[3])
-               : "v"(perm_addr), "v"(a0), "v"(a1), "v"(b0), "v"(b1));
+  r.d[0] = (unsigned)r.a; r.d[1] = (unsigned)(r.a >> 32); r.d[2] = (unsigned)r.b; r.d[3] = (unsigned)(r.b >> 32);
 }
 template <int QA, int N>
 __device__ __forceinline__ void ws_trp_store(GLOBAL_AS void* buf, int F, int s0, int mt, int lane, WsPiece& r) {
@@ -216,16 +186,9 @@ __device__ __forceinline__ void ws_trp_store(GLOBAL_AS void* buf, int F, int s0,
 #ifdef LAB4D_WSABL_NOST  // timing experiment (results wrong): reads and waits, no store
   return;
 #endif
-#ifdef LAB4D_ABL_L2STORE  // timing experiment (results wrong): every wave keeps writing the same 2048-sample window, so the stores never reach HBM
-  s0 &= 0x7ff;
-#endif
   GLOBAL_AS char* base = (GLOBAL_AS char*)buf + tile_base_offset<PBF16>(F, s0, 32 * mt);
-#ifdef LAB4D_WS_LINEAR_STORE
-  const unsigned lo = (unsigned)(lane * 16);
-#else
   const int i = lane & 15, G = lane >> 4, h = G & 1, S = G >> 1;
   const unsigned lo = (unsigned)((4 * h + (i & 3)) * 128 + (32 * S + 8 * (i >> 2)) * 2);
-#endif
   gst16(base + (lo + (unsigned)((16 * (QA >> 1) + 8 * (QA & 1)) * 128)), r.d[0], r.d[1], r.d[2], r.d[3]);
 }
 // Where the NPI pieces of one hosted tile set go in a loop of G k-groups with a B ring of depth BD: piece i is read at group I = (i G) / NPI, made
@@ -245,106 +208,14 @@ struct WsSpread {
   }
 };
 
-// -DLAB4D_WS_TRACE (measurement build, outputs wrong): the forward kernel sums, per wave, the shader cycles it spends in the phases of a layer
-// and waves 0 and 4 of workgroup 0 leave the sums in the first floats of `out` (tools/ws_compare.py --trace prints them)
-__device__ __forceinline__ unsigned long long ws_clock() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#ifdef LAB4D_WS_TRACE
-#define WS_T(i)                                   \
-  do {                                            \
-    const unsigned long long t_ = ws_clock();     \
-    tacc[i] += (float)(unsigned)(t_ - tlast);     \
-    tlast = t_;                                   \
-  } while (0)
-#else
-#define WS_T(i) \
-  do {          \
-  } while (0)
-#endif
-
 // End-of-layer barrier that also settles the scalar loads of the NEXT layer's pointers: the wait is the BUILTIN (the compiler's counter model
 // sees it: nothing scalar is pending afterwards), so the first LDS waits of the next layer are the hand-counted ones of the B ring and the first MFMA
 // waits for its own two reads only -- with a pointer load in flight the compiler has to wait lgkmcnt(0) (scalar loads return out of order), i.e. for
-// the whole ring prologue of all eight waves (trace build: 500-900 cycles per layer between the barrier and the first MFMA).
+// the whole ring prologue of all eight waves (500-900 cycles per layer between the barrier and the first MFMA, measured with a cycle trace).
 __device__ __forceinline__ void ws_layer_barrier() {
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0), vmcnt / expcnt untouched
   asm volatile("s_barrier" ::: "memory");
 }
-// ---- per-block progress counters (LAB4D_WS_SYNC = 1, round 5) -------------------------------------------------------------------------------
-// The per-layer s_barrier keeps all eight waves in lock-step: the two waves of a SIMD enter their MFMA loops together and leave them together, so the
-// matrix pipe idles while both run their epilogues (profiles/r04_ws_trace.json: the older wave of every SIMD parks 22-28 k of ~88 k cycles per tile at
-// the barrier).  What a layer really needs is per 64-sample BLOCK: item (layer l, block b) reads block b of layer l-1's output (all eight row tiles) and
-// overwrites block b of the buffer layer l-1 read -- both settled once every wave has finished ITS item (l-1, b).  So each wave counts itself into
-// cnt[b] when it is done with block b of a layer (its LDS writes are performed: the LDS pipe is in-order per wave and the wait in front of the add makes
-// it explicit) and polls cnt[b] before it touches block b of the next layer.  A wave that finishes early runs up to one item ahead of the slowest one;
-// the two waves of a SIMD drift out of phase and one's epilogue runs under the other's MFMAs.  Counters are monotone over the life of the workgroup
-// (8 arrivals per block and layer); the tile boundary keeps its full barriers (posenc scratch / embedding / head-gradient staging alias the buffers).
-// MEASURED (round 5, profiles/r05_ws_sync_token.json; ms per 4.2 M samples, fg base forward / backward, fg colour forward / backward):
-//   barrier (shipped)        5.996 / 6.796   3.142 / 3.100
-//   counters                 5.988 / 6.937   3.400 / 3.415
-//   counters + token         6.003 / 7.014   3.137 / 3.586
-//   barrier + token          6.427 / 7.278   3.212 / 3.273
-// i.e. NOT a win: the older wave of a SIMD no longer parks at the barrier, it parks in ws_wait_block instead (14-17 k of 86 k cycles per tile) -- the
-// critical path is the YOUNGER wave of each SIMD, which is busy the whole tile (its two loops run at half rate while the older wave's run beside them), and
-// one item of slack does not move work from it.  Bit-equal to the barrier build on hardware in every mode (tests/test_gpu_mlp_ws.py ran with
-// counters + token).  Kept as an experiment switch, default OFF.
-#ifndef LAB4D_WS_SYNC
-#define LAB4D_WS_SYNC 0
-#endif
-constexpr bool WS_SYNC = LAB4D_WS_SYNC != 0;
-__device__ __forceinline__ void ws_arrive(unsigned cnt_addr, int lane) {
-  // (memory clobber: the epilogue's LDS stores are emitted in front of this; lgkmcnt(0): they have been performed)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (lane == 0) {
-    const unsigned one = 1u;
-    asm volatile("ds_add_u32 %0, %1" ::"v"(cnt_addr), "v"(one) : "memory");
-  }
-}
-__device__ __forceinline__ void ws_wait_block(unsigned cnt_addr, unsigned target) {
-  unsigned v;
-  int spins = 0;
-  for (;;) {
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cnt_addr) : "memory");
-    if ((int)((unsigned)__builtin_amdgcn_readfirstlane((int)v) - target) >= 0) break;
-    if (++spins > (1 << 22)) __builtin_trap();  // a lost arrival must fail loudly, not hang the device
-    __builtin_amdgcn_s_sleep(1);
-  }
-}
-
-// ---- matrix-pipe token (LAB4D_WS_TOKEN = 1, round 5) ------------------------------------------------------------------------------------------
-// Two waves share a SIMD (wave w and w + 4).  Left alone they enter their MFMA loops together (each at half rate), leave them together and run their
-// epilogues together with the matrix pipe idle: profiles/r05_ws_trace_*.json -- the SIMD's pipe is busy 41 k of 85 k cycles per tile.  What
-// the dataflow wants is ALTERNATION: one wave streams its item through the pipe at full rate while the other converts / stores / waits.  The token is a
-// per-SIMD lock in LDS taken in front of an item's MFMA loop (behind the block wait) and dropped behind its last MFMA; nothing is waited for while it is
-// held (no deadlock), and the counters above let the other wave run its epilogue and the next item's entry in the meantime.
-// MEASURED (table above): slower.  A lone wave streams an item in ~1.45 k cycles (1,024 of them MFMA: the depth-2 B ring does not cover the LDS latency
-// without a second wave's instructions in between), so serialising the two waves' loops costs more than their overlapping epilogues return
-// (95 k instead of 85 k cycles per tile).  Experiment switch, default OFF.
-#ifndef LAB4D_WS_TOKEN
-#define LAB4D_WS_TOKEN 0
-#endif
-constexpr bool WS_TOKEN = LAB4D_WS_TOKEN != 0;
-__device__ __forceinline__ void ws_token_acquire(unsigned tok_addr, int lane) {
-  if constexpr (!WS_TOKEN) return;
-  const unsigned one = 1u;
-  int spins = 0;
-  for (;;) {
-    unsigned old = 1u;
-    if (lane == 0) asm volatile("ds_wrxchg_rtn_b32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(old) : "v"(tok_addr), "v"(one) : "memory");
-    if (__builtin_amdgcn_readfirstlane((int)old) == 0) break;  // (lane 0 is the first active lane)
-    if (++spins > (1 << 22)) __builtin_trap();
-    __builtin_amdgcn_s_sleep(1);
-  }
-}
-__device__ __forceinline__ void ws_token_release(unsigned tok_addr, int lane) {
-  if constexpr (!WS_TOKEN) return;
-  const unsigned zero = 0u;
-  if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(tok_addr), "v"(zero) : "memory");
-}
-
 template <class T>
 __device__ __forceinline__ void ws_pin_sgpr(T*& p) {
   unsigned long long v = (unsigned long long)p;
@@ -394,14 +265,9 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
   // frame).  Read from here a bias costs LDS reads, not vector-memory loads that queue -- in the in-order memory counter -- behind the tile stores
   // of the layer in front and hold up the first MFMA of every layer.
   __shared__ float bias_lds[NL * 256];
-  __shared__ unsigned int blk_cnt[2 + 4];  // [0..1] per 64-sample block: waves that have finished it, summed over the layers (see ws_arrive); [2..5] per SIMD: the matrix-pipe token
   const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const unsigned xbuf_lds = lds_addr(xbuf), ebuf_lds = lds_addr(ebuf), cnt_lds = lds_addr(blk_cnt), tok_lds = cnt_lds + 4u * (2u + (unsigned)(w & 3));
-  if constexpr (WS_SYNC || WS_TOKEN) {  // (the shipped barrier-only build neither initialises nor touches the counters / tokens: ADVICE r05)
-    if (tid < 6) blk_cnt[tid] = 0u;  // (the tile loop's first barrier is in front of every use)
-  }
-  unsigned cnt_base = 0u;          // arrivals per block before the current tile
+  const unsigned xbuf_lds = lds_addr(xbuf), ebuf_lds = lds_addr(ebuf);
   sfor<0, NL>([&](auto lc) {
     constexpr int l = decltype(lc)::value;
     if constexpr (TAN) {
@@ -412,7 +278,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
   });
   const unsigned trl = ws_tr_lane(lane), trl2 = trl ^ 32u;  // per-lane part of the transposing tile reads (unit stride 16 per n-tile): first / second read of a pair
   const int lane_s = ws_slot(lane);                          // this lane's slot inside a unit of the activation slabs
-  const unsigned perm_a = ws_perm_addr(lane);
 
   int S_eff = a.S, ntw = a.S_pad / WS_TILE;
   if (a.S_dev) {
@@ -426,24 +291,11 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
   // float per thread: sample pe_sl, axis pe_q) -- and the per-frame bias rows are refilled only when the tile's frame differs from the previous tile's (a
   // frame is 65,536 tiles long in the bench).  Before, every tile opened with a dependent HBM round trip that nothing could hide (all eight waves wait
   // for it at the tile's first barrier): -2 .. -4 % on the chains (profiles/r05_ws_prefetch.json).
-  // HIDE: the nets' heads have ONE row tile (sdf: 1 output, rgb / dense: 3), so in a tile's last layer only waves 0 and 1 have an item; waves 2 .. 7 --
-  // 384 threads = 128 samples x 3 axes -- evaluate the NEXT tile's positional encoding meanwhile (sincos, octave doubling, fp32 scratch rows), into the
-  // activation buffer the last layer does not read.  The tile then opens with the scratch -> B-unit conversion straight away: one barrier and the whole
-  // sincos phase (7-15 % of a tile, profiles/r05_ws_trace_call1.txt "posenc") leave the critical path.
-  // MEASURED (round 5, two boxes, profiles/r05_ws_prefetch.json): not a win -- fg base forward 5.89 -> 5.98 ms per 4.2 M samples, fg colour forward 3.01 -> 3.16
-  // (the six waves' sincos work competes for issue slots with the head item of waves 0 / 1, which is the layer's critical path, and the colour kernel
-  // spills 17 registers around it).  Experiment switch LAB4D_WS_HIDE_POSENC, default OFF; the tile-ahead fetch above stays.
-#ifndef LAB4D_WS_HIDE_POSENC
-#define LAB4D_WS_HIDE_POSENC 0
-#endif
-  constexpr bool HIDE = LAB4D_WS_HIDE_POSENC != 0 && !TAN && ws_mt<Net>(NL - 1) == 1 && NL >= 2;
-  constexpr int SCR_BUF = HIDE ? (((NL - 1) & 1) ^ 1) : 1;  // HIDE: the buffer the last layer's input is NOT in (its own output goes to HBM)
-  float* scr = reinterpret_cast<float*>(xbuf + SCR_BUF * WS_BUF);
+  float* scr = reinterpret_cast<float*>(xbuf + WS_BUF);  // the posenc scratch aliases activation buffer 1
   // (the thread -> (sample, axis) map is recomputed where it is used: three registers less across the MFMA loops)
 #define WS_PE_MAP                                                                             \
-  const int pe_t = HIDE ? tid - 128 : tid;                                                    \
-  const bool pe_on = pe_t >= 0 && pe_t < 384;                                                 \
-  const int pe_sl = pe_t & 127, pe_q = __builtin_amdgcn_readfirstlane((pe_t >> 7) & 3)
+  const bool pe_on = tid < 384;                                                               \
+  const int pe_sl = tid & 127, pe_q = __builtin_amdgcn_readfirstlane((tid >> 7) & 3)
   auto x_fetch = [&](int tile_, float& xp) {
     if constexpr (!TAN) {
       WS_PE_MAP;
@@ -478,12 +330,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
 #undef WS_PE_MAP
   float xcur = 0.f;
   x_fetch((int)blockIdx.x, xcur);
-  if constexpr (HIDE) {
-#ifndef LAB4D_WSABL_NOPOSENC
-    if ((int)blockIdx.x < ntw) posenc_rows(xcur);  // the first tile's; every later tile's is evaluated inside the previous tile's last layer
-#endif
-    wg_step_barrier();
-  }
   uint4 A[GMAX];  // this wave's row tile of the current layer's weights
   auto a_load = [&](auto g0c, auto g1c, const GLOBAL_AS void* Wp, int G, int mt) {
     constexpr int G0 = decltype(g0c)::value, G1 = decltype(g1c)::value;
@@ -501,10 +347,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
   const GLOBAL_AS void* Wn_c = KARG_PTR(FwdK, const void*, W, (NL > 1 ? 1 : 0));
   GLOBAL_AS void* act_c = nullptr;
   GLOBAL_AS unsigned int* mask_c = nullptr;
-#ifdef LAB4D_WS_TRACE
-  float tacc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  unsigned long long tlast = ws_clock();
-#endif
 
   int f_bias = -1;  // frame whose per-frame bias rows bias_lds holds
   for (int tile = blockIdx.x; tile < ntw; tile += gridDim.x) {
@@ -540,8 +382,7 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
         });
       }
     }
-    // ---- positional encoding, phase 1 (see posenc_rows); HIDE: already done inside the previous tile's last layer ----
-#ifndef LAB4D_WSABL_NOPOSENC
+    // ---- positional encoding, phase 1 (see posenc_rows) ----
     if constexpr (TAN) {
       // raw (S, KE) tangent rows -> the scratch rows the assembly below reads (16-byte pieces, coalesced; elements behind the last valid one repeat it,
       // like stage_in of the wave-resident kernel)
@@ -560,11 +401,10 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
         }
         *reinterpret_cast<float4*>(scr + row * ESTR + 4 * c4) = v;
       }
-    } else if constexpr (!HIDE) {
+    } else {
       posenc_rows(xcur);
     }
-#endif
-    if constexpr (!HIDE) wg_step_barrier();
+    wg_step_barrier();
     // ---- scratch -> B units (identity slot order: unit g of lane (n, h) = slots 16 g + 8 h + 0..7) + the stored [slot][sample] embedding ----
     for (int p = w; p < 2 * UE; p += 8) {
       const int b = p & 1, g = p >> 1;
@@ -596,7 +436,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
       }
     }
     wg_step_barrier();
-    WS_T(6);
 
     // ---- layers ----
 #pragma nounroll
@@ -610,10 +449,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
       constexpr bool LAST = (R == NL - 1);
       constexpr int MT = ws_mt<Net>(R), GE = ls.ke / 16, GA = ls.kin / 16, G = GE + GA;
       constexpr int Gn = ws_g<Net>((R + 1) % NL);  // A groups of the layer that follows (layer 0 of the next tile behind the last)
-#ifdef LAB4D_WS_TRACE
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trace build: how long the layer's first instructions would wait for the weights / the stores in front of them
-      WS_T(7);
-#endif
       using IT = WsItems<MT>;
       const GLOBAL_AS float* bl = KARG_PTR(FwdK, const float*, bias, l);
       const GLOBAL_AS float* pfl = KARG_PTR(FwdK, const float*, pf_bias, l);
@@ -625,7 +460,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
       uint4* xout = xbuf + (ib ^ 1) * WS_BUF;
       const int mt = IT::mt(w);
       const bool active = IT::active(w);
-      const unsigned cnt_tgt = cnt_base + 8u * (unsigned)l;  // every wave has finished layer l - 1 on a block once its counter reads this
 
       // bias (+ per-frame bias, which already contains the shared one: host contract) of item (mt, b) in accumulator layout
       // bias row from LDS (shared bias, or a tile inside one frame): four reads issued here, waited for (counted) behind the first item's ring prologue
@@ -662,10 +496,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
         }
       }
       f32x16_t bv[2];
-#ifdef LAB4D_WSABL_NOBIAS
-#pragma unroll
-      for (int r = 0; r < 16; ++r) bv[0][r] = bv[1][r] = 0.25f;
-#else
       if (active) {
         if (bias_lds_path) {
           const unsigned ba = lds_addr(bias_lds) + (unsigned)((l * 256 + 32 * mt + 4 * h) * 4);
@@ -678,7 +508,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
         }
         load_ext(IT::blk(w, 0));
       }
-#endif
       // ---- deferred stores of the layer in front: its tiles sit in this layer's input buffer.  Where this layer's MFMA loops can host them
       // (every wave has items here and had items there) they leave in pieces between the MFMAs (WsSpread); else as one burst here.
       constexpr int MTp = R > 0 ? ws_mt<Net>(R > 0 ? R - 1 : 0) : 1;
@@ -694,9 +523,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
       GLOBAL_AS void* act_n = KARG_PTR(FwdK, void*, act, l);
       GLOBAL_AS unsigned int* mask_n = KARG_PTR(FwdK, unsigned int*, mask, l);
       const int mtp = ITp::mt(w);
-      // a wave may count itself out of block b right behind item (l, b) when nothing it does later in this layer reads block b of the input buffer:
-      // two items per wave (one per block, in block order) whose hosted pieces -- the wave's own tiles of the layer in front -- belong to the item's block
-      constexpr bool EARLY = MT == 8 && (R == 0 || !SPREAD || MTp == 8);
       if constexpr (R > 0 && !SPREAD) {
         auto flush_prev = [&]() {
 #pragma unroll
@@ -714,9 +540,7 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
           }
         };
         if constexpr (ST) {
-#ifndef LAB4D_WSABL_NOFLUSH
           if (ITp::active(w)) flush_prev();
-#endif
         } else {
           if (actp != nullptr && ITp::active(w)) flush_prev();  // inference: only the layer another net consumes
         }
@@ -729,14 +553,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
           const int b = IT::blk(w, k);
           constexpr int KL = IT::IPW - 1;
           f32x16_t acc[2];
-          if constexpr (WS_SYNC || WS_TOKEN) {
-            WS_T(7);
-            if constexpr (WS_SYNC) {
-              if (l > 0) ws_wait_block(cnt_lds + 4u * (unsigned)b, cnt_tgt);
-            }
-            ws_token_acquire(tok_lds, lane);
-            WS_T(0);
-          }
           // B units stream from LDS through a ring of WS_BD k-groups (two n-tiles each): the read of group g + WS_BD is issued right behind the
           // MFMAs of group g.  Reads and waits are volatile asm (program order kept, counted waits written by hand): left to the scheduler the
           // reads sink next to their MFMAs (lgkmcnt(1) in front of every MFMA pair) and the LDS latency is exposed once per k-group.
@@ -745,9 +561,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
           const unsigned pe_a = ebuf_lds + (unsigned)((2 * b * UE) * 1024 + lane * 16), px_a = xbuf_lds + (unsigned)(ib * WS_BUF * 16 + (2 * b * 16) * 1024 + lane_s * 16);
           auto b_read = [&](auto gc, u32x4_t (&dst)[2]) {
             constexpr int g = decltype(gc)::value;
-#ifdef LAB4D_WSABL_HALFB  // timing experiment (results wrong): every second k-group reuses whatever the ring slot holds -- half the B reads, as if one read fed two MFMAs
-            if constexpr (g % 2 == 1) return;
-#endif
             if constexpr (g < GE) {
               ws_lds_read<g * 1024>(dst[0], pe_a);
               ws_lds_read<(UE + g) * 1024>(dst[1], pe_a);
@@ -757,7 +570,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
             }
           };
           sfor<0, BD>([&](auto gc) { b_read(gc, bq[decltype(gc)::value]); });
-#ifndef LAB4D_WSABL_NOBIAS
           if constexpr (k == 0) {
             if (bias_lds_path) {
               ws_lds_wait4<2 * BD>(br);  // the ring prologue (2 BD reads) was issued behind the four bias reads
@@ -769,7 +581,6 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
               bv[1] = bv[0];
             }
           }
-#endif
           acc[0] = bv[0];
           acc[1] = bv[1];
           sfor<0, G>([&](auto gc) {
@@ -793,26 +604,18 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
               using SP = WsSpread<G, (NPI > 0 ? NPI : 1)>;
               sfor<0, (SPREAD ? NPI : 0)>([&](auto ic) {
                 constexpr int i = decltype(ic)::value, pi = k * NPI + i, kp = pi / 4, qa = pi % 4;
-                if constexpr (SP::perm_at(i) == g) ws_trp_perm<SP::newer(SP::issue_at(i), true, g, BD)>(perm_a, tp);
+                if constexpr (SP::perm_at(i) == g) ws_trp_perm<SP::newer(SP::issue_at(i), true, g, BD)>(tp);
                 if constexpr (SP::store_at(i) == g) {
-#ifndef LAB4D_WSABL_NOFLUSH
                   ws_trp_store<qa, SP::newer(SP::perm_at(i), false, g, BD)>(actp, 32 * MTp, s0 + 64 * ITp::blk(w, kp), mtp, lane, tp);
                   if constexpr (!TAN && qa == 3 && Net::L[R > 0 ? R - 1 : 0].relu != 0) maskp[((size_t)(2 * tile + ITp::blk(w, kp)) * MTp + mtp) * 64 + lane] = pbits[kp];
-#endif
                 }
               });
             }
-#ifndef LAB4D_WSABL_NOAPF
             if (k == KL && g < Gn) A[g] = load_a(Wn, Gn, mtn, g, lane);  // the next layer's group g, right behind the last use of this one
-#endif
           });
-          ws_token_release(tok_lds, lane);
-          WS_T(1 + 2 * (k & 1));
           // requests of the next item (they have that item's matrix work to arrive)
           if (k < KL) {
-#ifndef LAB4D_WSABL_NOBIAS
             if constexpr (ls.pf != 0) load_bias(IT::blk(w, k + 1), bv);
-#endif
           }
           // ---- epilogue ----
           if constexpr (!LAST && ls.add_ext == 0) {
@@ -885,53 +688,21 @@ __global__ void __launch_bounds__(512) k_mlp_fwd_ws(FwdK a) {
               }
             }
           }
-          if constexpr (WS_SYNC && EARLY && !LAST) ws_arrive(cnt_lds + 4u * (unsigned)b, lane);
-          WS_T(2 + 2 * (k & 1));
         });
       } else {
         // a wave without an item in this layer still needs the next layer's weights
         a_load(std::integral_constant<int, 0>{}, std::integral_constant<int, (Gn < G ? Gn : G)>{}, Wn, Gn, mtn);
-        if constexpr (LAST && HIDE) {
-          static_assert(!LAST || !HIDE || IT::ITEMS == 2, "HIDE: the head's two items belong to waves 0 and 1");
-#ifndef LAB4D_WSABL_NOPOSENC
-          if (tile + (int)gridDim.x < ntw) posenc_rows(xnext);  // the NEXT tile's positional encoding, under the head's matrix work (see HIDE)
-#endif
-        }
       }
-      if constexpr (WS_SYNC && !LAST) {
-        if (!(EARLY && active)) {  // counted out of both blocks at the end of the layer
-          // ... and not before the layer in front is complete on BOTH: a wave with one item (or none) never waited on the other block, and its
-          // arrival there would be taken for a missing one of the layer in front (the counters are sums; found on hardware: fg_color's 4-row-tile layer)
-          if (l > 0) {
-            ws_wait_block(cnt_lds, cnt_tgt);
-            ws_wait_block(cnt_lds + 4u, cnt_tgt);
-          }
-          ws_arrive(cnt_lds, lane);
-          ws_arrive(cnt_lds + 4u, lane);
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // the scalar loads of the next layer's pointers (see ws_layer_barrier)
-      } else {
-        ws_layer_barrier();  // tile boundary (and every layer with LAB4D_WS_SYNC=0)
-      }
+      ws_layer_barrier();
       Wn_c = Wn_n;
       act_c = act_n;
       mask_c = mask_n;
       ws_pin_sgpr(Wn_c);
       ws_pin_sgpr(act_c);
       ws_pin_sgpr(mask_c);
-      WS_T(5);
     });
-    cnt_base += 8u * (unsigned)(NL - 1);  // NL - 1 counted layer ends per tile (the last layer ends at the tile's barrier)
     xcur = xnext;
   }
-#ifdef LAB4D_WS_TRACE
-  if (blockIdx.x == 0 && lane < 8 && a.out) {
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v = lane == i ? tacc[i] : v;
-    a.out[w * 8 + lane] = v;
-  }
-#endif
 }
 
 // =================================================================================================
@@ -995,17 +766,11 @@ __global__ void __launch_bounds__(512) k_mlp_bwd_ws(BwdK a) {
   constexpr int MTE_ANY = KE / 32;
   __shared__ uint4 xbuf[2 * WS_BUF];
   __shared__ float red[8 * 2 * 3 * 32];  // input-gradient partials of the embedding items: [wave][n-tile][axis][lane n]
-  __shared__ unsigned int blk_cnt[2 + 4];  // per-block progress counters (see ws_arrive) + per-SIMD matrix-pipe tokens
   const int tid = threadIdx.x, lane = tid & 63, n = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const unsigned xbuf_lds = lds_addr(xbuf), cnt_lds = lds_addr(blk_cnt), tok_lds = cnt_lds + 4u * (2u + (unsigned)(w & 3));
-  if constexpr (WS_SYNC || WS_TOKEN) {
-    if (tid < 6) blk_cnt[tid] = 0u;
-  }
-  unsigned cnt_base = 0u;
+  const unsigned xbuf_lds = lds_addr(xbuf);
   const unsigned trl = ws_tr_lane(lane), trl2 = trl ^ 32u;  // (see the forward kernel: slot swizzle of the slabs)
   const int lane_s = ws_slot(lane);
-  const unsigned perm_a = ws_perm_addr(lane);
   const int ntw = a.S_pad / WS_TILE;
   const bool want_dx = a.d_x != nullptr;
 
@@ -1120,7 +885,6 @@ __global__ void __launch_bounds__(512) k_mlp_bwd_ws(BwdK a) {
       const int rtn = wsb_first_tile<Net>(ln, w, want_dx);
       const int ib = (NL - 1 - l) & 1;
       uint4* xout = xbuf + (ib ^ 1) * WS_BUF;
-      const unsigned cnt_tgt = cnt_base + 8u * (unsigned)(NL - 1 - l);  // every wave has finished the layer above on a block once its counter reads this
       const bool act_on = DO_ACT && IT::active(w);
       const bool emb_on = MTE > 0 && want_dx && w < 2 * MTE;
       const int j = IT::mt(w);              // activation row tile of this wave
@@ -1148,8 +912,6 @@ __global__ void __launch_bounds__(512) k_mlp_bwd_ws(BwdK a) {
       constexpr bool SPREAD = NP > 0 && DO_ACT && IT::ITEMS >= 8 && ITp::ITEMS >= 8 && NP % NHOST == 0 && WsSpread<GK, (NPI > 0 ? NPI : 1)>::OK;
       GLOBAL_AS void* dzl = dz_c;
       const int jp = ITp::mt(w);
-      constexpr bool EARLY = DO_ACT && MTA == 8 && (NP == 0 || !SPREAD || MTp == 8);  // (see the forward kernel)
-      constexpr bool TOP = R == NL - 1, BOTTOM = R == 0;
       if constexpr (NP > 0 && !SPREAD) {
         if (ITp::active(w)) {
 #pragma unroll
@@ -1171,8 +933,6 @@ __global__ void __launch_bounds__(512) k_mlp_bwd_ws(BwdK a) {
         constexpr bool PF = decltype(pf_c)::value;
         constexpr int GP = decltype(gp_c)::value;
         constexpr int HK = decltype(host_c)::value;  // >= 0: this loop hosts the pieces HK NPI .. of the deferred dZ tiles
-        if constexpr (WS_SYNC && !TOP) ws_wait_block(cnt_lds + 4u * (unsigned)b, cnt_tgt);  // (the top layer's input is staged in front of the tile's barrier)
-        ws_token_acquire(tok_lds, lane);
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -1182,9 +942,6 @@ __global__ void __launch_bounds__(512) k_mlp_bwd_ws(BwdK a) {
         const unsigned px_a = xbuf_lds + (unsigned)(ib * WS_BUF * 16 + (2 * b * 16) * 1024 + lane_s * 16);
         auto b_read = [&](auto gc, u32x4_t (&dst)[2]) {
           constexpr int g = decltype(gc)::value;
-#ifdef LAB4D_WSABL_HALFB
-          if constexpr (g % 2 == 1) return;
-#endif
           ws_lds_read<g * 1024>(dst[0], px_a);
           ws_lds_read<(16 + g) * 1024>(dst[1], px_a);
         };
@@ -1210,13 +967,12 @@ __global__ void __launch_bounds__(512) k_mlp_bwd_ws(BwdK a) {
             using SP = WsSpread<GK, (NPI > 0 ? NPI : 1)>;
             sfor<0, (SPREAD ? NPI : 0)>([&](auto ic) {
               constexpr int i = decltype(ic)::value, pi = (HK >= 0 ? HK : 0) * NPI + i, kp = pi / 4, qa = pi % 4;
-              if constexpr (SP::perm_at(i) == g) ws_trp_perm<SP::newer(SP::issue_at(i), true, g, BD)>(perm_a, tp);
+              if constexpr (SP::perm_at(i) == g) ws_trp_perm<SP::newer(SP::issue_at(i), true, g, BD)>(tp);
               if constexpr (SP::store_at(i) == g) ws_trp_store<qa, SP::newer(SP::perm_at(i), false, g, BD)>(dzl, 32 * MTp, s0 + 64 * ITp::blk(w, kp), jp, lane, tp);
             });
           }
           if constexpr (PF && g < GP) A[g] = load_a(Wp, GP, rt, g, lane);
         });
-        ws_token_release(tok_lds, lane);
       };
 
       bool loaded_next = false;
@@ -1312,7 +1068,6 @@ __global__ void __launch_bounds__(512) k_mlp_bwd_ws(BwdK a) {
 #pragma unroll
               for (int q = 0; q < 2; ++q)
                 xout[((2 * b + t) * 16 + 2 * j + q) * 64 + lane_s] = make_uint4(pw[t][4 * q], pw[t][4 * q + 1], pw[t][4 * q + 2], pw[t][4 * q + 3]);
-            if constexpr (WS_SYNC && EARLY && !BOTTOM) ws_arrive(cnt_lds + 4u * (unsigned)b, lane);
           });
           loaded_next = true;
         }
@@ -1320,19 +1075,7 @@ __global__ void __launch_bounds__(512) k_mlp_bwd_ws(BwdK a) {
       if (!loaded_next) a_load(std::integral_constant<int, (GKn < GK ? GKn : GK)>{}, Wn, GKn, rtn);  // a wave without an item here still needs its next weights
       mcur[0] = mnext[0];
       mcur[1] = mnext[1];
-      if constexpr (WS_SYNC && !BOTTOM) {
-        if (!(EARLY && act_on)) {
-          if constexpr (!TOP) {  // (see the forward kernel: no arrival on a block before the layer above is complete there)
-            ws_wait_block(cnt_lds, cnt_tgt);
-            ws_wait_block(cnt_lds + 4u, cnt_tgt);
-          }
-          ws_arrive(cnt_lds, lane);
-          ws_arrive(cnt_lds + 4u, lane);
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-      } else {
-        ws_layer_barrier();  // tile boundary (and every layer with LAB4D_WS_SYNC=0)
-      }
+      ws_layer_barrier();
       Wn_c = Wn_n;
       dz_c = dz_n;
       maskq_c = maskq_n;
@@ -1341,7 +1084,6 @@ __global__ void __launch_bounds__(512) k_mlp_bwd_ws(BwdK a) {
       ws_pin_sgpr(maskq_c);
     });
 
-    cnt_base += 8u * (unsigned)(NL - 1);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll

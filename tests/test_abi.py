@@ -56,8 +56,9 @@ def test_library_targets_gfx950(so):
 
 
 def test_shipped_library_has_no_experiment_macros(so):
-    """The 40-odd LAB4D_ABL_* / LAB4D_WSABL_* / LAB4D_WS_TRACE ... switches in csrc/ are timing experiments (most give wrong results): the library the
-    product loads must have been compiled with none of them, and lab4d_build_flags() must know every such macro the sources test."""
+    """csrc/ keeps exactly two compile-time experiment switches, LAB4D_WSABL_NOST and LAB4D_ABL_WGRAD_L2 (timing ablations that give wrong results,
+    DESIGN.md section 8): the library the product loads must have been compiled with neither, the LAB4D_* macros the sources test must be exactly
+    these two (no new ones grow back), and lab4d_build_flags() must report exactly them."""
     import re
     so.lab4d_build_flags.restype = ctypes.c_char_p
     assert so.lab4d_build_flags() == b"", so.lab4d_build_flags()
@@ -66,11 +67,13 @@ def test_shipped_library_has_no_experiment_macros(so):
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".hpp")):
             src = open(os.path.join(csrc, f)).read()
-            tested |= set(re.findall(r"#\s*ifn?def\s+(LAB4D_[A-Z0-9_]+)", src)) | set(re.findall(r"defined\((LAB4D_[A-Z0-9_]+)\)", src))
+            tested |= set(re.findall(r"#\s*ifn?def\s+(LAB4D_[A-Z0-9_]+)", src)) | set(re.findall(r"defined\s*\(?\s*(LAB4D_[A-Z0-9_]+)", src))
+            tested |= set(re.findall(r"#\s*(?:el)?if\b[^\n]*?\b(LAB4D_[A-Z0-9_]+)", src))
     tested -= {"LAB4D_HIP_H"}
+    assert tested == {"LAB4D_WSABL_NOST", "LAB4D_ABL_WGRAD_L2"}, sorted(tested)
     runtime = open(os.path.join(csrc, "runtime.hip")).read()
     reported = set(re.findall(r"#ifdef (LAB4D_[A-Z0-9_]+)", runtime))
-    assert tested <= reported, sorted(tested - reported)
+    assert tested == reported, (sorted(tested), sorted(reported))
 
 
 def test_bad_arguments_are_rejected_without_a_gpu(so):

@@ -238,11 +238,6 @@ def time_case(net, S, report, dx_only=False):
             tf = 2.0 * S * mlp.NET_MACS[net] / (ms * 1e-3) / 1e12
             out["%s_%s_ms" % (what, "ws" if ws else "wave")] = round(ms, 3)
             out["%s_%s_frac_of_bf16_mfma_peak" % (what, "ws" if ws else "wave")] = round(tf / 2500.0, 4)
-        if ws and os.environ.get("LAB4D_WS_TRACE_PRINT"):
-            t = f["out"].view(-1)[:64].tolist()
-            ntile = (c["S_pad"] // 128 + 255) // 256
-            names = ["block_wait", "loop0", "epi0", "loop1", "epi1", "barrier", "posenc", "vmcnt@entry"]
-            out["trace_cycles_per_tile"] = {"wave%d" % wv: {names[i]: round(t[8 * wv + i] / ntile) for i in range(8)} for wv in range(8)}
         del f, b
         torch.cuda.empty_cache()
     print(json.dumps(out), flush=True)
