@@ -259,6 +259,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_rowmlp.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 11. Iso-surface extraction of the proxy-geometry refresh -- utils/geom_utils.py:442-503 (marching_cubes:
+ *     skimage.measure.marching_cubes + trimesh split), nnutils/nerf.py:303-343.  See lab4d_mesh.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_mesh.h"
+
 #ifdef __cplusplus
 }
 #endif

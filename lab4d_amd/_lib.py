@@ -131,10 +131,17 @@ SIGNATURES = {
     "lab4d_composite_forward": [vp, vp, ctypes.POINTER(FieldList), vp, vp, vp, ci, ci] + [vp] * 8 + [vp],
     "lab4d_composite_backward": [vp, vp, ctypes.POINTER(FieldList), vp, vp, vp, ci, ci] + [vp] * 5 + [vp, vp,
                                  ctypes.POINTER(FieldGrads), vp, vp, vp] + [vp],
+    # iso-surface extraction (include/lab4d_mesh.h; lab4d_amd/mesh.py)
+    "lab4d_mesh_work_ints": [ci, ci, ci],
+    "lab4d_mesh_count": [vp, vp, ci, ci, ci, cf, vp, vp, vp],
+    "lab4d_mesh_emit": [vp, ci, ci, ci, cf, vp, vp, ci, ci, vp, vp, vp],
+    "lab4d_mesh_component_work_ints": [ci, ci],
+    "lab4d_mesh_largest_component": [vp, vp, ci, ci, vp, vp, vp, vp, ctypes.POINTER(ci), vp],
 }
 
 
-INT64_RETURNS = ("lab4d_mlp_packed_bytes", "lab4d_compact_work_ints", "lab4d_skin_blend_backward_workspace_floats")  # host-only size queries
+INT64_RETURNS = ("lab4d_mlp_packed_bytes", "lab4d_compact_work_ints", "lab4d_skin_blend_backward_workspace_floats", "lab4d_mesh_work_ints",
+                 "lab4d_mesh_component_work_ints")  # host-only size queries
 
 
 def register(name, argtypes):
@@ -178,7 +185,7 @@ class _ProfiledLib:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if PROF is None or _TIMED_DEPTH > 0 or not name.startswith("lab4d_") or name in ("lab4d_last_error", "lab4d_arch", "lab4d_build_flags", "lab4d_mlp_fused_backward_supported", "lab4d_mlp_describe", "lab4d_mlp_packed_bytes", "lab4d_compact_work_ints", "lab4d_global_match_workspace_floats", "lab4d_skin_blend_backward_workspace_floats"):  # host-only
+        if PROF is None or _TIMED_DEPTH > 0 or not name.startswith("lab4d_") or name in ("lab4d_last_error", "lab4d_arch", "lab4d_build_flags", "lab4d_mlp_fused_backward_supported", "lab4d_mlp_describe", "lab4d_mlp_packed_bytes", "lab4d_compact_work_ints", "lab4d_global_match_workspace_floats", "lab4d_skin_blend_backward_workspace_floats", "lab4d_mesh_work_ints", "lab4d_mesh_component_work_ints"):  # host-only
             return fn
 
         def call(*a):

@@ -1,0 +1,120 @@
+"""Iso-surface extraction on the device (include/lab4d_mesh.h, csrc/mesh.hip): the marching-cubes step of the proxy-geometry refresh,
+which the reference runs on the host through skimage + trimesh (lab4d/utils/geom_utils.py:442-503).  Volume in, welded indexed triangle
+mesh out, optionally reduced to its largest connected component; the output is deterministic (see the header for the ordering contract)."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+# host <- device copies of the last marching_cubes call: "readbacks" counts every one (the {n_verts, n_faces} pair of the extraction, the
+# pair of the component filter, and the filter's looks at its convergence flags); "label_passes" / "label_readbacks" are the filter's own
+LAST = {"readbacks": 0, "label_passes": 0, "label_readbacks": 0}
+
+
+class Mesh:
+    """What the device mesher hands to code written for trimesh.Trimesh when trimesh is not installed: `.vertices` (V, 3) float32 and
+    `.faces` (F, 3) int32 as numpy arrays (NeRF.update_aabb / update_near_far and nerf.py:223 read them that way), `.bounds` (2, 3) or
+    None for an empty mesh -- trimesh's convention."""
+
+    def __init__(self, vertices, faces):
+        self.vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        self.faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+
+    @property
+    def bounds(self):
+        if self.vertices.shape[0] == 0:
+            return None
+        return np.stack([self.vertices.min(0), self.vertices.max(0)], 0)
+
+    def __repr__(self):
+        return "lab4d_amd.mesh.Mesh(vertices=%d, faces=%d)" % (self.vertices.shape[0], self.faces.shape[0])
+
+
+def _read_pair(counts):
+    """The one way values leave the device here: a 2-int tensor -> two Python ints."""
+    LAST["readbacks"] += 1
+    a, b = counts.tolist()
+    return int(a), int(b)
+
+
+def _xform(origin, step, device):
+    if not any(torch.is_tensor(t) for t in (origin, step)) and tuple(origin) == (0, 0, 0) and tuple(step) == (1, 1, 1):
+        return None  # index space: the kernel skips the transform
+    parts = [t.to(device=device, dtype=torch.float32).reshape(3) if torch.is_tensor(t) else torch.tensor([float(x) for x in t], dtype=torch.float32, device=device)
+             for t in (origin, step)]
+    return torch.cat(parts).contiguous()  # (device tensors stay on the device: no host copy of a box that lives there)
+
+
+def keep_largest_component(verts, faces):
+    """Largest connected component of an indexed triangle mesh on the device (geom_utils.py:497-501): vertices joined by a face, size =
+    number of vertices, ties to the component that holds the smallest vertex index; survivors keep their order.  Returns (verts, faces)."""
+    _lib.require_device(verts, faces)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("lab4d_amd.mesh: output sizes depend on the data (host read-backs); it cannot run under stream capture")
+    if verts.dtype != torch.float32 or faces.dtype != torch.int32 or verts.ndim != 2 or faces.ndim != 2 or verts.shape[1] != 3 or faces.shape[1] != 3:
+        raise RuntimeError("lab4d_amd.mesh.keep_largest_component needs verts (V, 3) float32 and faces (F, 3) int32")
+    V, F = verts.shape[0], faces.shape[0]
+    if V == 0:
+        return verts, faces
+    lib = _lib.lib()
+    work = torch.empty(int(lib.lab4d_mesh_component_work_ints(V, F)), dtype=torch.int32, device=verts.device)
+    out_v, out_f = torch.empty_like(verts), torch.empty_like(faces)
+    counts = torch.empty(2, dtype=torch.int32, device=verts.device)
+    stats = (ctypes.c_int * 2)()
+    _lib.check(lib.lab4d_mesh_largest_component(_lib.ptr(verts), _lib.ptr(faces), V, F, _lib.ptr(work), _lib.ptr(out_v), _lib.ptr(out_f), _lib.ptr(counts),
+                                                stats, _lib.stream()), "mesh_largest_component")
+    LAST["label_passes"], LAST["label_readbacks"] = int(stats[0]), int(stats[1])
+    LAST["readbacks"] += int(stats[1])
+    nv, nf = _read_pair(counts)
+    return out_v[:nv], out_f[:nf]
+
+
+def marching_cubes(sdf, mask=None, level=0.0, origin=(0, 0, 0), step=(1, 1, 1), largest_component=False):
+    """Iso-surface `sdf == level` of a (Gx, Gy, Gz) float32 device volume (last axis fastest) as (verts (V, 3) float32, faces (F, 3) int32)
+    device tensors.  mask (same shape, bool / uint8, optional): a cell is meshed iff all 8 of its corners are set (and finite); a value is
+    inside iff it is < level, the face normals point towards increasing values.  Vertices are origin + step * (index-space position), per
+    axis; origin / step may be sequences or device tensors of 3.  largest_component: keep the connected component with the most vertices.
+    An empty surface gives (0, 3) tensors.  One device-to-host read (the two sizes) without the filter."""
+    _lib.require_device(sdf, mask)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("lab4d_amd.mesh: output sizes depend on the data (host read-backs); it cannot run under stream capture")
+    if sdf.ndim != 3 or sdf.dtype != torch.float32:
+        raise RuntimeError("lab4d_amd.mesh.marching_cubes needs a (Gx, Gy, Gz) float32 volume, got %s %s" % (tuple(sdf.shape), sdf.dtype))
+    if mask is not None:
+        if mask.shape != sdf.shape or mask.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError("lab4d_amd.mesh.marching_cubes: mask must be bool / uint8 of the volume's shape")
+        mask = mask.view(torch.uint8)
+    LAST.update(readbacks=0, label_passes=0, label_readbacks=0)
+    lib = _lib.lib()
+    Gx, Gy, Gz = (int(g) for g in sdf.shape)
+    n_work = int(lib.lab4d_mesh_work_ints(Gx, Gy, Gz))
+    if n_work < 0:
+        raise RuntimeError("lab4d_amd.mesh.marching_cubes: unsupported grid %d x %d x %d (every dimension >= 1, fewer than 2^31 / 3 points)" % (Gx, Gy, Gz))
+    dev = sdf.device
+    xf = _xform(origin, step, dev)
+    work = torch.empty(n_work, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.check(lib.lab4d_mesh_count(_lib.ptr(sdf), _lib.ptr(mask), Gx, Gy, Gz, float(level), _lib.ptr(work), _lib.ptr(counts), _lib.stream()), "mesh_count")
+    V, F = _read_pair(counts)
+    verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    if V == 0:
+        return verts, faces
+    _lib.check(lib.lab4d_mesh_emit(_lib.ptr(sdf), Gx, Gy, Gz, float(level), _lib.ptr(xf), _lib.ptr(work), V, F, _lib.ptr(verts), _lib.ptr(faces), _lib.stream()),
+               "mesh_emit")
+    if largest_component:
+        return keep_largest_component(verts, faces)
+    return verts, faces
+
+
+def to_mesh_object(verts, faces):
+    """Device result -> the object reference code expects from geom_utils.marching_cubes: a trimesh.Trimesh (process=False: nothing is
+    merged or re-ordered) when trimesh imports, else a Mesh."""
+    v, f = verts.detach().cpu().numpy(), faces.detach().cpu().numpy()
+    try:
+        import trimesh
+    except ImportError:
+        return Mesh(v, f)
+    return trimesh.Trimesh(vertices=v, faces=f, process=False)

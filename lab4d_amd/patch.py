@@ -57,10 +57,16 @@ N_DEPTH = 64
 _PREC_NAMES = {"bf16": mlp.PREC_BF16, "f32": mlp.PREC_F32}
 
 
-def configure(module, precision=None, n_depth=None):
+def configure(module, precision=None, n_depth=None, mesher=None):
     """Per-model settings: every sub-module of `module` (a dvr_model, a MultiFields, one field, one warp ...) runs its kernels at this
-    precision ("bf16" / "f32") / with this many samples per ray, whatever the process-wide defaults of patch() are."""
+    precision ("bf16" / "f32") / with this many samples per ray, whatever the process-wide defaults of patch() are.
+    mesher="device": NeRF.extract_canonical_mesh extracts the iso-surface with lab4d_amd.mesh (no skimage / trimesh needed) instead of
+    handing the volumes to the reference's geom_utils.marching_cubes; mesher="reference" switches back.  Default: the reference's."""
+    if mesher not in (None, "device", "reference"):
+        raise ValueError("lab4d_amd.patch.configure: mesher must be 'device' or 'reference', got %r" % (mesher,))
     for m in module.modules():
+        if mesher is not None:
+            m._lab4d_amd_mesher = mesher
         if precision is not None:
             m._lab4d_amd_precision = _PREC_NAMES[precision] if isinstance(precision, str) else int(precision)
         if n_depth is not None:
@@ -562,16 +568,26 @@ def nerf_extract_canonical_mesh(self, grid_size=64, level=0.0, inst_id=None, use
     visibility field, the per-sample work of the proxy refresh -- is ONE inference-mode launch per network over the whole grid
     (lab4d_amd.proxy.grid_query: 0.7 ms at 64^3); iso-surface extraction, the unit-cube -> box transform and the connected-component filter
     stay the reference's own `geom_utils.marching_cubes` (CPU skimage / trimesh), which is handed the two finished volumes through the
-    sdf_func / visibility_func it asks for chunk by chunk."""
+    sdf_func / visibility_func it asks for chunk by chunk.
+    With configure(field, mesher="device") those three steps run on the device as well (lab4d_amd.proxy.extract_mesh, the reference's
+    1 / grid_size spacing) and geom_utils is not touched; the mesh comes back as a trimesh.Trimesh(process=False) when trimesh imports,
+    else as a lab4d_amd.mesh.Mesh (.vertices / .faces / .bounds)."""
     import importlib
     from . import proxy
-    geom = importlib.import_module("lab4d.utils.geom_utils")
+    device_mesher = getattr(self, "_lab4d_amd_mesher", None) == "device"
+    geom = None if device_mesher else importlib.import_module("lab4d.utils.geom_utils")
     P = field_params(self)
     dev = P["logibeta"].device if "logibeta" in P else next(self.parameters()).device
     iid = None if inst_id is None else torch.tensor([inst_id], device=dev)
     code_base = inst_code(self.basefield, iid, 1, dev)
     code_vis = inst_code(self.vis_mlp.basefield, iid, 1, dev)
     alpha = getattr(self.pos_embedding, "alpha", None)
+    if device_mesher:
+        from . import mesh as _mesh
+        verts, faces, _ = proxy.extract_mesh(P, self.aabb, grid_size=grid_size, level=level, code_base=code_base, code_vis=code_vis, prec=_prec(self),
+                                             use_visibility=use_visibility, extend=0.5 if use_extend_aabb else 0.0, alpha=alpha, kind=field_kind(self),
+                                             largest_component=self.category == "fg")
+        return _mesh.to_mesh_object(verts, faces)
     with torch.no_grad():
         # (round 5, ADVICE r04: the bg field is a NeRF too -- multifields.py:86-93 -- and MultiFields.update_geometry_aux meshes every field)
         sdf, vis, box = proxy.grid_query(P, self.aabb, grid_size=grid_size, code_base=code_base, code_vis=code_vis, prec=_prec(self),

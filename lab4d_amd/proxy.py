@@ -4,12 +4,14 @@ utils/geom_utils.py:392-476) -- and the bound updates that follow it, `NeRF.upda
 (nerf.py:345-376, geom_utils.py:344-362).
 
 The grid query is the chain kernels' inference mode (nothing stored, MFMA-bound): one "frame" of grid_size^3 samples under one
-instance code, sdf head only (no density, no colour), then the visibility net.  Marching cubes itself is the reference's CPU
-`skimage.measure.marching_cubes` on the returned volume (out of the hot path); what comes back from it -- the vertices / bounds
-of the new proxy mesh -- goes into `update_aabb` / `update_near_far` here, which keep `aabb` and `near_far` on the device."""
+instance code, sdf head only (no density, no colour), then the visibility net.  Marching cubes is either the reference's CPU
+`skimage.measure.marching_cubes` on the returned volume, or -- `extract_mesh` -- the device mesher of lab4d_amd/mesh.py on the volume
+where it lies; the vertices / bounds of the new proxy mesh go into `update_aabb` / `update_near_far` here, which keep `aabb` and
+`near_far` on the device."""
 import torch
 
 from . import deformable as DF
+from . import mesh as _mesh
 from . import mlp
 from . import quat_utils as Q
 
@@ -50,6 +52,27 @@ def grid_query(P, aabb, grid_size=64, code_base=None, code_vis=None, prec=mlp.PR
     sdf = torch.cat(sdf, 0).view(G, G, G)
     vis = torch.cat(vis, 0).view(G, G, G) if use_visibility else torch.ones(G, G, G, dtype=torch.bool, device=sdf.device)
     return sdf, vis, box
+
+
+@torch.no_grad()
+def extract_mesh(P, aabb, grid_size=64, level=0.0, code_base=None, code_vis=None, prec=mlp.PREC_BF16, use_visibility=True, extend=0.5, alpha=None,
+                 kind="fg", largest_component=False, exact_spacing=False):
+    """geom_utils.marching_cubes (geom_utils.py:442-503) without leaving the device: `grid_query` + lab4d_amd.mesh.marching_cubes on the two
+    volumes (visibility as the mask: a cell is meshed iff all 8 of its corners are visible) + the bounds of the result.  Returns
+    (verts (V, 3) float32, faces (F, 3) int32, bounds (2, 3) or None for an empty surface), all device tensors, so `update_aabb(aabb, bounds)`
+    and `update_near_far(..., verts, ...)` can follow with no host copy of the mesh.  largest_component: the reference's
+    apply_connected_component (fg fields, nerf.py:339-342).
+    Spacing: the reference meshes with spacing = 1 / grid_size (geom_utils.py:486) and scales by the box (geom_utils.py:495), although
+    sample_grid puts index grid_size - 1 on the far face of the box; its meshes are therefore shrunk by (G - 1) / G towards the low corner.
+    exact_spacing=False (default) reproduces that: step = (hi - lo) / G; True puts the vertices where the samples were taken:
+    step = (hi - lo) / (G - 1)."""
+    sdf, vis, box = grid_query(P, aabb, grid_size, code_base=code_base, code_vis=code_vis, prec=prec, use_visibility=use_visibility, extend=extend,
+                               alpha=alpha, kind=kind)
+    step = (box[1] - box[0]) / float(grid_size - 1 if exact_spacing else grid_size)
+    verts, faces = _mesh.marching_cubes(sdf.contiguous(), vis.contiguous() if use_visibility else None, level=level, origin=box[0], step=step,
+                                        largest_component=largest_component)
+    bounds = torch.stack([verts.min(0)[0], verts.max(0)[0]], 0) if verts.shape[0] else None
+    return verts, faces, bounds
 
 
 def grid_to_world(verts01, box):
