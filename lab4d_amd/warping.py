@@ -2,7 +2,6 @@
 transforms.get_bone_coords, geom_utils.dual_quaternion_skinning, loss_utils.cross_entropy_skin_loss)
 on the gfx950 kernels of csrc/skinning.hip and the fused delta-skin MLP (LAB4D_NET_SKIN)."""
 import os
-import types
 
 import torch
 from torch.autograd import Function
@@ -53,44 +52,42 @@ class BoneCoords(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        xyz, art_r, art_d, gauss = ctx.saved_tensors
-        S, (M, B) = xyz.shape[0], art_r.shape[:2]
-        g = g.contiguous()
-        gx = torch.empty_like(xyz)
-        need_p = any(ctx.needs_input_grad[1:4])
-        if need_p and ctx.spf % 256 == 0 and os.environ.get("LAB4D_BONE_FUSE", "1") != "0":
-            # one pass over the (S,3B) gradient: the point gradient and the per-frame Gram matrix of the parameter path together
-            G = torch.empty(M, 3 * B, 4, device=xyz.device)
-            with _lib.timed("k_bone_bwd_x+gram", (2.0 * S * 3 * B * 4, 4.0 * S * (3 + 3 + 3 * B))):
-                _lib.check(_lib.lib().lab4d_bone_coords_backward_gram(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(gauss), _lib.ptr(g), S, ctx.spf, M, B,
-                                                                      _lib.ptr(gx), _lib.ptr(G), _lib.stream()), "bone_coords_backward_gram")
-            need_r, need_d, need_g = ctx.needs_input_grad[1:4]
-            gar = torch.empty_like(art_r) if need_r else None
-            gad = torch.empty_like(art_d) if need_d else None
-            gg = torch.zeros_like(gauss) if need_g else None
-            _lib.check(_lib.lib().lab4d_bone_params_from_gram(_lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(G), M, B, _lib.ptr(gar),
-                                                              _lib.ptr(gad), _lib.ptr(gg), _lib.stream()), "bone_params_from_gram")
-            return gx, gar, gad, gg, None
+        return (*bone_coords_backward(ctx.saved_tensors, ctx.spf, ctx.needs_input_grad[1:4], g), None)
+
+
+def bone_coords_backward(saved, spf, need, g):
+    """BoneCoords' adjoint: saved = (xyz, art_r, art_d, gauss) as the forward took them, need = which of art_r, art_d, gauss want a gradient,
+    g (S,3B) the coordinate gradient.  Returns (gx, gar, gad, gg)."""
+    xyz, art_r, art_d, gauss = saved
+    need_r, need_d, need_g = need
+    S, (M, B) = xyz.shape[0], art_r.shape[:2]
+    g = g.contiguous()
+    gx = torch.empty_like(xyz)
+    if any(need) and spf % 256 == 0 and os.environ.get("LAB4D_BONE_FUSE", "1") != "0":
+        # one pass over the (S,3B) gradient: the point gradient and the per-frame Gram matrix of the parameter path together
+        G = torch.empty(M, 3 * B, 4, device=xyz.device)
+        with _lib.timed("k_bone_bwd_x+gram", (2.0 * S * 3 * B * 4, 4.0 * S * (3 + 3 + 3 * B))):
+            _lib.check(_lib.lib().lab4d_bone_coords_backward_gram(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(gauss), _lib.ptr(g), S, spf, M, B,
+                                                                  _lib.ptr(gx), _lib.ptr(G), _lib.stream()), "bone_coords_backward_gram")
+    else:
         with _lib.timed("k_bone_bwd_x", (0.0, 4.0 * S * (3 + 3 * B))):
-            _lib.check(_lib.lib().lab4d_bone_coords_backward(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(g), S, ctx.spf,
+            _lib.check(_lib.lib().lab4d_bone_coords_backward(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(g), S, spf,
                                                              M, B, _lib.ptr(gx), None, None, None, _lib.stream()), "bone_coords_backward")
         # parameter gradients: out[s,b,:] = (R_b x_s + t_b) / gauss_b is affine in x_s, so every one of them is a function
         # of the per-frame Gram matrix G[m,b,k,j] = sum_{s in m} g[s,b,k] [x_s,1]_j: one tall-skinny product on the device
-        if not any(ctx.needs_input_grad[1:4]):
-            return gx, None, None, None, None
+        if not any(need):
+            return gx, None, None, None
         xh = torch.cat([xyz, torch.ones_like(xyz[:, :1])], -1)
         G = torch.zeros(M, 3 * B, 4, device=xyz.device)
         with _lib.timed("k_gram_pf_rb(bone)", (2.0 * S * 3 * B * 4, 4.0 * S * (3 * B + 4))):
-            _lib.check(_lib.lib().lab4d_gram_per_frame(_lib.ptr(g), 3 * B, _lib.ptr(xh), 4, S, ctx.spf, M, _lib.ptr(G), _lib.stream()), "gram_per_frame")
-        # (M,B)-sized chain rule: one thread per (frame, bone) (csrc/skinning.hip k_bone_param_from_gram)
-        need_r, need_d, need_g = ctx.needs_input_grad[1:4]
-        gar = torch.empty_like(art_r) if need_r else None
-        gad = torch.empty_like(art_d) if need_d else None
-        gg = torch.zeros_like(gauss) if need_g else None
-        if need_r or need_d or need_g:
-            _lib.check(_lib.lib().lab4d_bone_params_from_gram(_lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(G), M, B, _lib.ptr(gar),
-                                                              _lib.ptr(gad), _lib.ptr(gg), _lib.stream()), "bone_params_from_gram")
-        return gx, gar, gad, gg, None
+            _lib.check(_lib.lib().lab4d_gram_per_frame(_lib.ptr(g), 3 * B, _lib.ptr(xh), 4, S, spf, M, _lib.ptr(G), _lib.stream()), "gram_per_frame")
+    # (M,B)-sized chain rule: one thread per (frame, bone) (csrc/skinning.hip k_bone_param_from_gram)
+    gar = torch.empty_like(art_r) if need_r else None
+    gad = torch.empty_like(art_d) if need_d else None
+    gg = torch.zeros_like(gauss) if need_g else None
+    _lib.check(_lib.lib().lab4d_bone_params_from_gram(_lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(G), M, B, _lib.ptr(gar),
+                                                      _lib.ptr(gad), _lib.ptr(gg), _lib.stream()), "bone_params_from_gram")
+    return gx, gar, gad, gg
 
 
 def bone_affine(art_r, art_d, gauss):
@@ -107,25 +104,26 @@ class SkinChain(Function):
     """BoneCoords followed by the delta-skin MLP (skinning.py:89-124) with the (S,3B) bone coordinates never written: the chain
     kernel forms them from the points and the per-frame affine table while it stages its input tile (lab4d_mlp_fwd_args.aff).
     The backward pass is the two existing ones back to back: the chain's input gradient (S,3B) feeds k_bone_bwd_x and the
-    per-frame Gram reduction of BoneCoords.backward.  Arguments after gauss are those of mlp.MlpChain after x2."""
+    per-frame Gram reduction of BoneCoords.backward.  Arguments after gauss: the number of per-frame tables, the tables, then [weight, bias] per layer (mlp.chain_forward)."""
+
+    N_LEAD = 8  # inputs in front of the per-frame tables
 
     @staticmethod
     def forward(ctx, net, prec, spf, xyz, art_r, art_d, gauss, n_pf, *rest):
         xyz = xyz.contiguous()
-        inner = types.SimpleNamespace(needs_input_grad=(False, False, False, True, False, False, False, False, False) + tuple(ctx.needs_input_grad[8:]))
-        out = mlp.MlpChain.forward(inner, net, prec, spf, xyz, None, None, -1, n_pf, None, *rest, aff=bone_affine(art_r, art_d, gauss))
-        ctx.inner, ctx.spf = inner, spf
+        need = ctx.needs_input_grad[SkinChain.N_LEAD:]  # of the per-frame tables and the parameters; the coordinate gradient is always wanted
+        out, _, ctx.chain = mlp.chain_forward(net, prec, spf, xyz, rest[:n_pf], rest[n_pf:], mlp.Wants(x=True, pfs=need[:n_pf], params=need[n_pf:]),
+                                              aff=bone_affine(art_r, art_d, gauss))
+        ctx.spf = spf
         ctx.save_for_backward(xyz, art_r.contiguous(), art_d.contiguous(), gauss.contiguous())
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_out):
-        res = mlp.MlpChain.backward(ctx.inner, d_out)
-        bone_ctx = types.SimpleNamespace(saved_tensors=ctx.saved_tensors, spf=ctx.spf, needs_input_grad=(True,) + tuple(ctx.needs_input_grad[4:7]) + (False,))
-        gx, gar, gad, gg, _ = BoneCoords.backward(bone_ctx, res[3])
-        ctx.inner = None
-        return (None, None, None, gx, gar, gad, gg, None) + tuple(res[9:])
+        g_coord, _, _, g_pfs, g_params = mlp.chain_backward(ctx.chain, d_out)
+        gx, gar, gad, gg = bone_coords_backward(ctx.saved_tensors, ctx.spf, ctx.needs_input_grad[4:7], g_coord)
+        return (None, None, None, gx, gar, gad, gg, None, *g_pfs, *g_params)
 
 
 class BoneAffine(Function):
@@ -174,22 +172,19 @@ class SkinChainA(Function):
     weight-gradient launch for linear_1, no (S, 3B) coordinate gradient and no pass over it (k_bone_bwd_x + Gram): the backward chain kernel
     returns the point gradient (S,3) and dL/dWf (M,64,4) directly."""
 
+    N_LEAD = 5  # inputs in front of the parameters
+
     @staticmethod
     def forward(ctx, net, prec, spf, xyz, tab, *params):
-        xyz = xyz.contiguous()
-        need = any(ctx.needs_input_grad)
-        inner = types.SimpleNamespace(needs_input_grad=(False, False, False, need, False, False, False, False, False) + tuple(ctx.needs_input_grad[5:]))
-        out = mlp.MlpChain.forward(inner, net, prec, spf, xyz, None, None, -1, 0, None, *params, aff=tab.detach().contiguous())
-        ctx.inner = inner
+        want = mlp.Wants(x=any(ctx.needs_input_grad), params=ctx.needs_input_grad[SkinChainA.N_LEAD:])
+        out, _, ctx.chain = mlp.chain_forward(net, prec, spf, xyz.contiguous(), (), params, want, aff=tab.detach().contiguous())
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_out):
-        res = mlp.MlpChain.backward(ctx.inner, d_out)
-        g_tab = ctx.inner.g_aff
-        ctx.inner = None
-        return (None, None, None, res[3], g_tab) + tuple(res[9:])
+        d_x, _, _, _, g_params = mlp.chain_backward(ctx.chain, d_out)
+        return (None, None, None, d_x, ctx.chain.g_aff, *g_params)
 
 
 # The delta-skin MLP runs in its per-frame affine form (SkinChainA); 0 restores the bone-coordinate form (SkinChain) for A/B measurements.
@@ -358,7 +353,7 @@ def skin_logits(P, x, art, t_embed, code, M, spf, prec, pre=None):
         params += [P[bd[l].wname], P[bd[l].bname]]
     if not FUSE_BONE_COORDS:
         bone = BoneCoords.apply(x, art[0], art[1], gauss, spf)  # (S,3B): input of the delta-skin MLP only
-        return mlp.MlpChain.apply(net, prec, spf, bone, None, None, -1, 1, None, pf, *params), gauss
+        return mlp.MlpChain.apply(net, prec, spf, bone, None, None, -1, 1, None, None, pf, *params), gauss
     return SkinChain.apply(net, prec, spf, x, art[0], art[1], gauss, 1, pf, *params), gauss
 
 

@@ -357,3 +357,53 @@ def test_fused_narrow_backward_equals_the_stored_activation_path(net_name, monke
     for a, b, n in zip(g1, g0, names):
         e = float((a - b).norm() / (b.norm() + 1e-30))
         assert e < 2e-2 and cosine(a, b.cpu()) > 0.999, (n, e)
+
+
+@pytest.mark.parametrize("prec", [0, 1])
+def test_a_tap_belongs_to_the_call_it_was_passed_to(prec):
+    """run_chain(tap=d) / eikonal_sdf(tap=...) that fail before their launch (a Python KeyError on a missing weight name -- nothing happens on
+    the device) leave nothing behind: d stays empty, and later calls of other nets compute what they compute in a fresh state.
+    The tap is an argument of MlpChain.apply / EikonalSdf.apply.  When it travelled through a module global that run_chain armed on its first
+    line, the failed call left the global armed until the next run_chain overwrote it; a chain in between that does not come through run_chain
+    -- the delta-skin field, warping.skin_logits -- took the stranger's dict for its own, filled it and gave up its fused backward.  The
+    `d == {}` directly after skin_logits is the assertion that form fails; the NET_VIS and eikonal steps hold in both forms (run_chain re-arms
+    on entry, and eikonal_sdf looks its weights up before it hands the tap on) and pin that the values do not move."""
+    from lab4d_amd import mlp, warping
+    M, N, D = 2, 4, 64
+    spf = N * D
+    P, fr, xyz, g = setup(31, M, N, D)
+    Pl = {k: (v.to(DEV).clone().requires_grad_(True) if v.dtype.is_floating_point else v.to(DEV)) for k, v in P.items()}
+    code_vis, code_base = fr["code_vis"].to(DEV), fr["code_base"].to(DEV)
+    x = xyz.reshape(-1, 3).to(DEV)
+    w = torch.rand(M * spf, 1, generator=g).to(DEV)
+    keys = GRAD_KEYS["vis"]
+
+    def vis():
+        xg = x.clone().requires_grad_(True)
+        out = mlp.run_chain(mlp.NET_VIS, prec, Pl, xg, spf, conds={0: code_vis})
+        return [out.detach()] + list(torch.autograd.grad((out * w).sum(), [xg] + [Pl[k] for k in keys]))
+
+    fresh = vis()
+    d = {}
+    with pytest.raises(KeyError):
+        mlp.run_chain(mlp.NET_FG_BASE, prec, {k: v for k, v in Pl.items() if k != "sdf.weight"}, x, spf, conds={0: code_base, 4: code_base}, tap=d)
+    assert d == {}
+    # the next chain that does not come through run_chain, directly after the failed call
+    art = tuple(t.to(DEV) for t in fr["t_articulation"])
+    warping.skin_logits(Pl, x, art, fr["t_embed"].to(DEV), fr["code_skin"].to(DEV), M, spf, prec)
+    assert d == {}
+    after = vis()
+    assert torch.equal(after[0], fresh[0]) and torch.equal(after[1], fresh[1])  # output, point gradient
+    for k, a, b in zip(keys, after[2:], fresh[2:]):  # the weight-gradient kernels add their block partials atomically: equal up to the order of those additions
+        assert rel_err(a, b.cpu()) < 1e-5, (k, rel_err(a, b.cpu()))
+    assert d == {}
+
+    # the eikonal term on the first two rays (blocks 0, 1 of the field pass); the failed call is handed the pattern of blocks 5, 6
+    tapped = {}
+    mlp.run_chain(mlp.NET_FG_BASE, prec, Pl, x, spf, conds={0: code_base, 4: code_base}, tap=tapped)
+    assert tapped.get("emb") is not None
+    xe, ray_code = x[:2 * D], code_base[[0, 0]]
+    e_fresh = mlp.eikonal_sdf(Pl, xe, ray_code, D, prec)
+    with pytest.raises(KeyError):
+        mlp.eikonal_sdf(Pl, xe, ray_code, D, prec, prefix="nope.", tap=(tapped, torch.tensor([5, 6], device=DEV)))
+    assert torch.equal(mlp.eikonal_sdf(Pl, xe, ray_code, D, prec, tap=None), e_fresh)

@@ -95,3 +95,51 @@ def test_first_layer_through_the_column_map_equals_the_reference_layer():
         Wk = torch.stack([W[:, c] if c >= 0 else torch.zeros(W.shape[0]) for c in cm.tolist()], -1)  # what lab4d_mlp_pack gathers
         got = slots @ Wk.t() + mlp.pf_bias_of(net, 0, W, code) + b
         assert torch.allclose(got, ref, atol=1e-5), wname
+
+
+# The per-net tables as they stood before they were derived from mlp.NETS (bench.py, the tests and tools/ read them by these names).
+NET_NAMES = {0: "fg_base", 1: "fg_color", 2: "vis", 3: "feat", 4: "skin", 5: "dense", 6: "bg_base", 7: "bg_color", 8: "skin18", 9: "hash_geo", 10: "hash_color", 11: "dense6",
+             12: "skin_a", 13: "skin18_a"}
+KERNEL_NET = {0: "FgBase", 1: "FgColor", 2: "Vis", 3: "Feat", 4: "Skin", 5: "Dense", 6: "BgBase", 7: "BgColor", 8: "Skin18", 9: "HashGeo", 10: "HashColor", 11: "Dense6", 12: "SkinA",
+              13: "Skin18A"}
+NET_MACS = {0: 572928 + 256, 1: 158464 + 37248, 2: 10240, 3: 77568, 4: 20736, 5: 39 * 256 + 256 * 256 + 256 * 3,
+            6: 100096 + 128, 7: 43392 + 8576, 8: (54 + 160) * 64 + 64 * 64 + 64 * 18, 9: 32 * 64 + 64 * 16, 10: 19 * 64 + 64 * 64 + 64 * 3,
+            11: 199 * 256 + 3 * 256 * 256 + 455 * 256 + 256 * 256 + 256 * 3,
+            12: 4 * 64 + 64 * 64 + 64 * 25, 13: 4 * 64 + 64 * 64 + 64 * 18}
+WS_NETS = (0, 1, 5, 11)
+
+
+def test_per_net_tables_keep_their_contents():
+    """NET_NAMES, KERNEL_NET, NET_MACS and WS_NETS are derived from one record per net (mlp.NETS): same keys, types and values as the literal
+    tables they replace, and the NET_* constants name the same ids."""
+    assert mlp.NET_NAMES == NET_NAMES and mlp.KERNEL_NET == KERNEL_NET and mlp.NET_MACS == NET_MACS
+    for table in (mlp.NET_NAMES, mlp.KERNEL_NET, mlp.NET_MACS):
+        assert type(table) is dict and list(table) == list(range(14))
+    assert mlp.WS_NETS == WS_NETS and type(mlp.WS_NETS) is tuple
+    assert all(type(v) is int for v in mlp.NET_MACS.values())
+    assert {n: getattr(mlp, "NET_" + name.upper()) for n, name in NET_NAMES.items()} == {n: n for n in range(14)}
+
+
+def test_bindings_of_every_net_match_the_recorded_ones(golden_dir):
+    """bindings(net) for all 14 nets against tests/golden/mlp_bindings.json -- (wname, bname, emb0, cond, prev0, aux0) per layer, recorded from the
+    one-branch-per-net form of bindings() before it was built from the two layer-pattern helpers -- and against the library's own description:
+    one binding per layer, a conditioning block exactly where the layer takes a per-frame bias."""
+    import json
+    import os
+    snap = json.load(open(os.path.join(golden_dir, "mlp_bindings.json")))
+    assert sorted(snap) == sorted(NET_NAMES.values())
+    for net, name in NET_NAMES.items():
+        d, bds = mlp.describe(net), mlp.bindings(net)
+        assert len(bds) == d.n_layers, name
+        assert [[b.wname, b.bname, b.emb0, list(b.cond) if b.cond else None, b.prev0, b.aux0] for b in bds] == snap[name], name
+        for layer, b in enumerate(bds):
+            assert bool(d.layers[layer].pf_bias) == (b.cond is not None), (name, layer)
+        assert [(b.wname, b.bname) for b in mlp.bindings(net, "pre.")] == [("pre." + b.wname, "pre." + b.bname) for b in bds], name
+
+
+def test_mask_numel_is_one_lane_word_per_tile_and_32_features():
+    for prec, tile in ((mlp.PREC_BF16, 64), (mlp.PREC_F32, 32)):
+        for mout_pad in (32, 64, 256):
+            for S_pad in (256, 512):
+                L = mlp.LayerDesc(mout_pad=mout_pad)
+                assert mlp.mask_numel(L, S_pad, prec) == (S_pad // tile) * (mout_pad // 32) * 64

@@ -65,7 +65,7 @@ def run_fwd(c, ws):
             r["act"][l] = torch.zeros(mlp.buf_numel(L.mout_pad, S_pad), dtype=torch.bfloat16, device="cuda")
             a.act[l] = _lib.dp(r["act"][l])
         if c["train"] and L.relu and l + 1 < NL:
-            r["mask"][l] = torch.zeros((S_pad // 64) * (L.mout_pad // 32) * 64, dtype=torch.int32, device="cuda")
+            r["mask"][l] = torch.zeros(mlp.mask_numel(L, S_pad, BF), dtype=torch.int32, device="cuda")
             a.mask[l] = _lib.dp(r["mask"][l])
     if c["train"]:
         r["emb"] = torch.zeros(mlp.buf_numel(d.ke, S_pad), dtype=torch.bfloat16, device="cuda")
