@@ -265,6 +265,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_mesh.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 12. Occupancy bit grid of the hash field: empty-space skipping per sample and per ray (not in the reference, parity unpinned).
+ *     See lab4d_occgrid.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_occgrid.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,10 @@ SIGNATURES = {
     "lab4d_mesh_emit": [vp, ci, ci, ci, cf, vp, vp, ci, ci, vp, vp, vp],
     "lab4d_mesh_component_work_ints": [ci, ci],
     "lab4d_mesh_largest_component": [vp, vp, ci, ci, vp, vp, vp, vp, ctypes.POINTER(ci), vp],
+    # occupancy bit grid of the hash field (include/lab4d_occgrid.h; lab4d_amd/occgrid.py)
+    "lab4d_occgrid_update": [vp, vp, vp, vp, ci, cf, cf, vp],
+    "lab4d_occgrid_mask": [vp, vp, vp, ci, ctypes.c_long, vp, vp],
+    "lab4d_occgrid_ray_span": [vp, vp, vp, vp, vp, ci, ctypes.c_long, vp, vp, vp],
 }
 
 
