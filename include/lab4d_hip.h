@@ -271,6 +271,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_occgrid.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 13. Packed ray marching through the occupied cells and ragged compositing of the packed sample list (not in the reference, parity
+ *     unpinned).  See lab4d_packed.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_packed.h"
+
 #ifdef __cplusplus
 }
 #endif

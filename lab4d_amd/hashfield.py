@@ -13,13 +13,15 @@ Parameters live in a flat dict like every other net here: "hash.table" (L, 2^log
 
 Empty-space skipping: an occgrid.OccupancyGrid (a bit per cell of a coarse grid over the box; include/lab4d_occgrid.h) is refreshed from the
 field's density with update_occupancy() and handed to forward_compacted(occ=...), whose compaction then also drops the samples in empty cells;
-grid.ray_depths() places a ray's samples between its first and last occupied cell.  All of it is opt-in.
+grid.ray_depths() places a ray's samples between its first and last occupied cell.  render_packed() goes all the way: the rays are marched at a
+fixed step through the occupied cells only (packed.march), the field runs on the packed list of kept samples, and the list is composited per ray
+(packed.composite); nothing of size rays x samples-per-ray exists.  All of it is opt-in.
 """
 import math
 
 import torch
 
-from . import hashgrid, mlp
+from . import hashgrid, mlp, packed
 from . import render_utils as RU
 from .deformable import volsdf_density
 
@@ -114,3 +116,17 @@ def forward_compacted(P, cfg, xyz, dirs, cap, prec=mlp.PREC_F32, res=None, get_d
     if not get_density:
         d_c = d_c * live.to(d_c.dtype)  # (forward() masks density and colour, not the raw sdf)
     return RU.scatter_rows_ad(rgb_c, idx, count, S), RU.scatter_rows_ad(d_c, idx, count, S), count, overflow
+
+
+def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None):
+    """Renders rays through the hash field with packed marching (include/lab4d_packed.h): packed.march(grid, origin, dir, t_range, dt, cap, k_max)
+    keeps the candidates t0 + (k + 0.5) dt of every ray whose cell's bit is set -- what forward_compacted(occ=grid) keeps of the same lattice --
+    as one packed list of at most `cap` rows (STATIC: the call is capturable), forward() runs on those rows (the parked rows behind the count lie
+    outside the box: zero encoding, masked), and packed.composite renders colour and depth per ray with delta = dt * |dir|.  origin, dir (R,3) in the
+    field's frame, t_range (R,2).  Returns (rgb (R,3), mask (R,1), depth (R,1), total (1,) int32 = kept samples before the capacity, overflow (1,) bool =
+    total > cap: samples were dropped, callers check it where they synchronise anyway).  A ray without a kept sample renders zeros.  Gradients flow
+    to the table, the Linears and logibeta."""
+    rays = packed.march(grid, origin, dir, t_range, dt, cap, k_max=k_max)
+    rgb_s, dens_s = forward(P, cfg, rays.xyz, rays.dirs, spf=max(int(cap), 1), prec=prec, res=res, table_grad_f16=table_grad_f16)
+    rendered, mask = packed.composite(dens_s, rays.deltas, {"rgb": rgb_s, "depth": rays.t[:, None]}, rays)
+    return rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow

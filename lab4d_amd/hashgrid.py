@@ -10,6 +10,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from . import packed  # noqa: F401  (not used here: tests/test_abi.py imports this module, not hashfield, and expects a signature for every declared symbol)
 
 vp, ci = _lib.vp, _lib.ci
 _lib.register("lab4d_hashgrid_forward", [vp, vp, vp, ci, ci, ci, ci, vp, vp])

@@ -1,0 +1,157 @@
+"""Packed ray marching and ragged compositing of the hash field (include/lab4d_packed.h, csrc/packed.hip): `march` steps every ray at a fixed
+step through the occupied cells of an occgrid.OccupancyGrid and emits the kept samples of all rays as ONE packed list with a per-ray
+(start, count); `composite` renders that list directly.  Nothing of size rays x samples-per-ray exists.  The reference has no counterpart
+(nnutils/nerf.py:98 is a TODO); the rules are written down in the header and in csrc/packed_math.hpp.  Nothing here synchronises with the
+host: every call can be captured in a hipGraph."""
+import ctypes
+import math
+
+import torch
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+
+vp, ci, cl, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
+_lib.register("lab4d_packed_march_count", [vp, vp, vp, vp, vp, ci, cl, cf, ci, vp, vp])
+_lib.register("lab4d_packed_march_write", [vp, vp, vp, vp, vp, ci, cl, cf, ci, vp, cl] + [vp] * 8 + [vp])
+_lib.register("lab4d_packed_composite_forward", [vp, vp, ctypes.POINTER(_lib.FieldList), vp, vp, cl, cl, vp, vp, vp, vp, vp])
+_lib.register("lab4d_packed_composite_backward", [vp, vp, ctypes.POINTER(_lib.FieldList), vp, vp, cl, cl, vp, vp, vp, vp, ctypes.POINTER(_lib.FieldGrads), vp])
+
+
+def _f32(name, t, *tail):
+    _lib.require_device(t)
+    if t.dtype != torch.float32 or t.ndim != len(tail) + 1 or tuple(t.shape[1:]) != tail:
+        raise RuntimeError("lab4d_amd.packed: %s must be float32 (n%s), got %s %s" % (name, "".join(", %d" % x for x in tail), t.dtype, tuple(t.shape)))
+
+
+class PackedRays:
+    """The packed sample list of one march.  Per row (cap rows): t (cap,) the ray parameter, deltas (cap,) = dt * |dir| of the row's ray,
+    xyz (cap,3), dirs (cap,3) unit view directions, ray_idx (cap,) int32.  Per ray (R): ray_start, ray_count int32 -- ray r owns rows
+    ray_start[r] .. + ray_count[r], in ascending t; ray_count is cut at the capacity.  total (1,) int32: the untruncated number of kept
+    samples; overflow (1,) bool: total > cap (samples were dropped).  Rows behind min(total, cap) are parked outside the box with
+    ray_idx = -1, t = 0, deltas = 0."""
+    __slots__ = ("t", "deltas", "xyz", "dirs", "ray_idx", "ray_start", "ray_count", "total", "overflow", "R", "cap")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+@torch.no_grad()
+def march(grid, origin, dir, t_range, dt, cap, k_max=1024):
+    """grid: occgrid.OccupancyGrid; origin, dir (R,3), t_range (R,2) = [t0, t1] in the units of `dir`; dt > 0 the step in those units;
+    cap: the STATIC number of packed rows; k_max: at most this many candidates t0 + (k + 0.5) dt per ray.  -> PackedRays.  Two kernels
+    (count, write) around one prefix sum; no read-back."""
+    _f32("origin", origin, 3)
+    _f32("dir", dir, 3)
+    _f32("t_range", t_range, 2)
+    R, dt, cap, k_max = origin.shape[0], float(dt), int(cap), int(k_max)
+    if dir.shape[0] != R or t_range.shape[0] != R:
+        raise RuntimeError("lab4d_amd.packed.march: origin %s, dir %s and t_range %s disagree on the number of rays"
+                           % (tuple(origin.shape), tuple(dir.shape), tuple(t_range.shape)))
+    if not (math.isfinite(dt) and dt > 0):
+        raise RuntimeError("lab4d_amd.packed.march: dt = %r must be finite and > 0" % dt)
+    if k_max < 1:
+        raise RuntimeError("lab4d_amd.packed.march: k_max = %d must be >= 1" % k_max)
+    if R * k_max >= 1 << 31:
+        raise RuntimeError("lab4d_amd.packed.march: R * k_max = %d * %d does not fit 31 bits" % (R, k_max))
+    if not 0 <= cap < 1 << 31:
+        raise RuntimeError("lab4d_amd.packed.march: cap = %d outside [0, 2^31)" % cap)
+    dev = origin.device
+    origin, dir, t_range = origin.detach(), dir.detach(), t_range.detach()
+    count = torch.empty(R, dtype=torch.int32, device=dev)
+    head = (_lib.ptr(origin), _lib.ptr(dir), _lib.ptr(t_range), _lib.ptr(grid.aabb), _lib.ptr(grid.bits), grid.G, R, dt, k_max)
+    _lib.check(_lib.lib().lab4d_packed_march_count(*head, _lib.ptr(count), _lib.stream()), "packed_march_count")
+    start = torch.cumsum(count, 0, dtype=torch.int32) - count  # (the exclusive scan: R * k_max < 2^31, the sums fit)
+    out = {"t": torch.empty(cap, device=dev), "deltas": torch.empty(cap, device=dev), "xyz": torch.empty(cap, 3, device=dev),
+           "dirs": torch.empty(cap, 3, device=dev), "ray_idx": torch.empty(cap, dtype=torch.int32, device=dev),
+           "ray_count": torch.empty(R, dtype=torch.int32, device=dev), "total": torch.empty(1, dtype=torch.int32, device=dev)}
+    overflow = torch.empty(1, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().lab4d_packed_march_write(*head, _lib.ptr(start), cap, _lib.ptr(out["t"]), _lib.ptr(out["deltas"]), _lib.ptr(out["xyz"]),
+                                                   _lib.ptr(out["dirs"]), _lib.ptr(out["ray_idx"]), _lib.ptr(out["ray_count"]), _lib.ptr(out["total"]),
+                                                   _lib.ptr(overflow), _lib.stream()), "packed_march_write")
+    return PackedRays(ray_start=start, overflow=overflow.view(torch.bool), R=R, cap=cap, **out)
+
+
+def _field_list(fields, modes):
+    fl = _lib.FieldList()
+    fl.n_fields = len(fields)
+    sumC = 0
+    for i, (f, m) in enumerate(zip(fields, modes)):
+        fl.fields[i] = _lib.dp(f)
+        fl.channels[i] = f.shape[-1]
+        fl.modes[i] = m
+        sumC += 1 if m == 2 else f.shape[-1]
+    return fl, sumC
+
+
+class _PackedComposite(Function):
+    @staticmethod
+    def forward(ctx, density, deltas, ray_start, ray_count, modes, *fields):
+        P, R = density.shape[0], ray_start.shape[0]
+        fl, sumC = _field_list(fields, modes)
+        mask = torch.empty(R, 1, device=density.device)
+        out = torch.empty(R, max(sumC, 1), device=density.device)
+        _lib.check(_lib.lib().lab4d_packed_composite_forward(_lib.ptr(density), _lib.ptr(deltas), fl, _lib.ptr(ray_start), _lib.ptr(ray_count), R, P, None, None,
+                                                             _lib.ptr(mask), _lib.ptr(out), _lib.stream()), "packed_composite_forward")
+        ctx.save_for_backward(density, deltas, ray_start, ray_count, *fields)
+        ctx.modes = tuple(modes)
+        return mask, out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_mask, g_out):
+        density, deltas, ray_start, ray_count, *fields = ctx.saved_tensors
+        P, R = density.shape[0], ray_start.shape[0]
+        fl, _ = _field_list(fields, ctx.modes)
+        gf = _lib.FieldGrads()
+        gf.n_fields = len(fields)
+        gfields = []
+        for i, f in enumerate(fields):
+            g = torch.zeros_like(f) if ctx.needs_input_grad[5 + i] else None  # (zeros: the rows that no ray owns are not written)
+            gfields.append(g)
+            gf.fields[i] = _lib.dp(g) if g is not None else None
+        g_density = torch.zeros_like(density) if ctx.needs_input_grad[0] else None
+        g_deltas = torch.zeros_like(deltas) if ctx.needs_input_grad[1] else None
+        g_mask = g_mask.contiguous() if g_mask is not None else None
+        g_out = g_out.contiguous() if g_out is not None else None
+        _lib.check(_lib.lib().lab4d_packed_composite_backward(_lib.ptr(density), _lib.ptr(deltas), fl, _lib.ptr(ray_start), _lib.ptr(ray_count), R, P,
+                                                              _lib.ptr(g_mask), _lib.ptr(g_out), _lib.ptr(g_density), _lib.ptr(g_deltas), gf, _lib.stream()),
+                   "packed_composite_backward")
+        return (g_density, g_deltas, None, None, None, *gfields)
+
+
+def composite(density, deltas, fields, rays, modes=None):
+    """density, deltas (P,) or (P,1) on the packed rows of `rays` (a PackedRays, or anything with ray_start / ray_count (R,) int32);
+    fields: dict name -> (P, c); modes: dict name -> 0 (weights normalised by mask + 1e-6; the default), 1 (the same, weights detached),
+    2 (plain mean over the ray's samples and channels).  -> (rendered: dict name -> (R, c), or (R,) for a mode-2 field; mask (R,1)).
+    A ray without samples renders zeros.  Differentiable in density, deltas and the fields."""
+    names = list(fields)
+    if len(names) > 16:
+        raise RuntimeError("lab4d_amd.packed.composite: more than 16 fields")
+    ms = [int((modes or {}).get(k, 0)) for k in names]
+    if any(m not in (0, 1, 2) for m in ms):
+        raise RuntimeError("lab4d_amd.packed.composite: modes are 0, 1 or 2, got %s" % ms)
+    _lib.require_device(density, deltas, rays.ray_start, rays.ray_count, *fields.values())
+    P = density.shape[0]
+    if density.numel() != P or deltas.numel() != P or density.dtype != torch.float32 or deltas.dtype != torch.float32:
+        raise RuntimeError("lab4d_amd.packed.composite: density %s and deltas %s must be float32 (P,) or (P, 1)" % (tuple(density.shape), tuple(deltas.shape)))
+    fs = []
+    for k in names:
+        f = fields[k]
+        if f.dtype != torch.float32 or f.ndim != 2 or f.shape[0] != P or not 1 <= f.shape[1] <= 64:
+            raise RuntimeError("lab4d_amd.packed.composite: field %s must be float32 (%d, 1..64), got %s %s" % (k, P, f.dtype, tuple(f.shape)))
+        fs.append(f)
+    if sum(1 if m == 2 else f.shape[1] for f, m in zip(fs, ms)) > 64:
+        raise RuntimeError("lab4d_amd.packed.composite: more than 64 output channels")
+    rs, rc = rays.ray_start, rays.ray_count
+    if rs.dtype != torch.int32 or rc.dtype != torch.int32 or rs.ndim != 1 or rs.shape != rc.shape:
+        raise RuntimeError("lab4d_amd.packed.composite: ray_start / ray_count must be int32 (R,)")
+    mask, out = _PackedComposite.apply(density.reshape(P), deltas.reshape(P), rs, rc, tuple(ms), *fs)
+    rendered, co = {}, 0
+    for k, m, f in zip(names, ms, fs):
+        c = 1 if m == 2 else f.shape[1]
+        rendered[k] = out[:, co] if m == 2 else out[:, co:co + c]
+        co += c
+    return rendered, mask
