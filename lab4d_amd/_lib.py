@@ -6,6 +6,7 @@ missing or a call fails, a RuntimeError is raised.
 """
 import ctypes
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -101,59 +102,74 @@ def build(force=False, verbose=True):
 
 
 _LIB = None
-vp, ci, cu, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_float
+vp, ci = ctypes.c_void_p, ctypes.c_int
+
+# The prototypes in include/*.h are the single source of the ctypes signatures: nothing on the Python side lists or counts arguments.
+_SCALARS = {"int": ci, "int32_t": ci, "uint32_t": ctypes.c_uint32, "float": ctypes.c_float, "long": ctypes.c_long, "int64_t": ctypes.c_int64,
+            "long long": ctypes.c_longlong}
+_RETURNS = {"int": ci, "long": ctypes.c_long, "int64_t": ctypes.c_int64, "long long": ctypes.c_longlong, "const char*": ctypes.c_char_p}
+_PROTOTYPE = re.compile(r"^[ \t]*([A-Za-z_][\w \t*]*?)\s*\b(lab4d_\w+)\s*\(([^()]*)\)\s*;", re.M)
 
 
+def parse_prototypes(text, where):
+    """C header text -> {name: (restype, params, has_stream)} for every `<return type> lab4d_<name>(<params>);` in it.  A parameter is a ctypes
+    scalar type, c_void_p for a data pointer, or the C NAME of a lab4d_* struct for a pointer to one (argtypes() gives it its type).  A type
+    outside the closed maps above raises: there is no default."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    out = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        proto = "%s %s(%s)" % (ret.strip(), name, " ".join(params.split()))
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RETURNS:
+            raise TypeError("%s: return type '%s' of `%s` is not one of %s" % (where, ret, proto, sorted(_RETURNS)))
+        args = []
+        for p in [] if params.strip() in ("", "void") else params.split(","):
+            words = [w for w in p.replace("*", " * ").split() if w != "const"]
+            if "*" in words:
+                args.append(words[0] if words[0].startswith("lab4d_") else vp)
+            else:  # `<type> <name>` or a bare `<type>`
+                key = " ".join(words) if " ".join(words) in _SCALARS else " ".join(words[:-1])
+                if key not in _SCALARS:
+                    raise TypeError("%s: parameter '%s' of `%s` is neither a pointer nor one of %s" % (where, p.strip(), proto, sorted(_SCALARS)))
+                args.append(_SCALARS[key])
+        out[name] = (_RETURNS[ret], args, bool(re.search(r"\bstream\s*(,|$)", params)))
+    return out
+
+
+SIGNATURES = {}  # name -> (restype, params, has_stream) of every prototype in include/*.h
+for _h in sorted(os.listdir(INCLUDE)):
+    if _h.endswith(".h"):
+        with open(os.path.join(INCLUDE, _h)) as _fh:
+            SIGNATURES.update(parse_prototypes(_fh.read(), "include/" + _h))
+MIRRORS = {}  # C struct name -> its ctypes.Structure mirror
+
+
+def argtypes(params, mirrors=MIRRORS):
+    """The ctypes argtypes of a parsed parameter list: a struct pointer is POINTER(mirror) once the mirror is bound, c_void_p until then (which
+    takes no Structure: such a function cannot be called without the module that builds the struct)."""
+    return [(ctypes.POINTER(mirrors[p]) if p in mirrors else vp) if isinstance(p, str) else p for p in params]
+
+
+def mirrors(c_name):
+    """Class decorator: binds a ctypes.Structure to the C struct it mirrors (tests/test_abi.py holds every bound mirror against a C compiler)."""
+    def bind(cls):
+        MIRRORS[c_name] = cls
+        if _LIB is not None:
+            for name, (_, params, _) in SIGNATURES.items():
+                if c_name in params:
+                    getattr(_LIB, name).argtypes = argtypes(params)
+        return cls
+    return bind
+
+
+@mirrors("lab4d_field_list")
 class FieldList(ctypes.Structure):
     _fields_ = [("n_fields", ci), ("fields", vp * 16), ("channels", ci * 16), ("modes", ci * 16)]
 
 
+@mirrors("lab4d_field_grads")
 class FieldGrads(ctypes.Structure):
     _fields_ = [("n_fields", ci), ("fields", vp * 16)]
-
-
-# name -> argtypes; the single source of truth for the exported symbols (tests check that every
-# symbol declared in include/*.h is listed here and resolves in the .so)
-SIGNATURES = {
-    "lab4d_quaternion_mul_forward": [vp, vp, vp, cu, cu, cu, ci, vp],
-    "lab4d_quaternion_mul_backward": [vp, cu, cu, cu, vp, vp, vp, vp, ci, vp],
-    "lab4d_quaternion_mul_backward_backward": [vp, vp, cu, cu, cu, vp, vp, vp, vp, vp, vp, ci, vp],
-    "lab4d_quaternion_conjugate": [vp, cu, vp, ci, vp],
-    "lab4d_mat3x3_det_forward": [vp, vp, cu, ci, vp],
-    "lab4d_mat3x3_scale_adjoint_forward": [vp, vp, vp, cu, ci, vp],
-    "lab4d_mat3x3_inv_forward": [vp, vp, vp, cu, ci, vp],
-    "lab4d_mat3x3_inv_backward": [vp, vp, vp, cu, ci, vp],
-    "lab4d_ray_samples_forward": [vp] * 6 + [ci] * 3 + [vp] * 6 + [vp],
-    "lab4d_ray_samples_backward": [vp] * 6 + [ci] * 3 + [vp] * 5 + [vp] * 3 + [vp],
-    "lab4d_sample_pdf": [vp, vp, ci, ci, ci, cf, vp, vp, vp],
-    "lab4d_sample_pdf_u": [vp, vp, vp, ci, ci, ci, cf, vp, vp, vp],
-    "lab4d_sort_depth": [vp, ci, vp, ci, ci, vp, vp],
-    "lab4d_composite_forward": [vp, vp, ctypes.POINTER(FieldList), vp, vp, vp, ci, ci] + [vp] * 8 + [vp],
-    "lab4d_composite_backward": [vp, vp, ctypes.POINTER(FieldList), vp, vp, vp, ci, ci] + [vp] * 5 + [vp, vp,
-                                 ctypes.POINTER(FieldGrads), vp, vp, vp] + [vp],
-    # iso-surface extraction (include/lab4d_mesh.h; lab4d_amd/mesh.py)
-    "lab4d_mesh_work_ints": [ci, ci, ci],
-    "lab4d_mesh_count": [vp, vp, ci, ci, ci, cf, vp, vp, vp],
-    "lab4d_mesh_emit": [vp, ci, ci, ci, cf, vp, vp, ci, ci, vp, vp, vp],
-    "lab4d_mesh_component_work_ints": [ci, ci],
-    "lab4d_mesh_largest_component": [vp, vp, ci, ci, vp, vp, vp, vp, ctypes.POINTER(ci), vp],
-    # occupancy bit grid of the hash field (include/lab4d_occgrid.h; lab4d_amd/occgrid.py)
-    "lab4d_occgrid_update": [vp, vp, vp, vp, ci, cf, cf, vp],
-    "lab4d_occgrid_mask": [vp, vp, vp, ci, ctypes.c_long, vp, vp],
-    "lab4d_occgrid_ray_span": [vp, vp, vp, vp, vp, ci, ctypes.c_long, vp, vp, vp],
-}
-
-
-INT64_RETURNS = ("lab4d_mlp_packed_bytes", "lab4d_compact_work_ints", "lab4d_skin_blend_backward_workspace_floats", "lab4d_mesh_work_ints",
-                 "lab4d_mesh_component_work_ints")  # host-only size queries
-
-
-def register(name, argtypes):
-    SIGNATURES[name] = argtypes
-    if _LIB is not None:
-        fn = getattr(_LIB, name)
-        fn.argtypes = argtypes
-        fn.restype = ctypes.c_int64 if name in INT64_RETURNS else ci
 
 
 def lib():
@@ -164,32 +180,30 @@ def lib():
             raise RuntimeError(
                 "liblab4d_hip.so is missing (%s). Build it with `python -c 'import __graft_entry__ as g; g.build()'`; "
                 "lab4d_amd has no CPU or eager-PyTorch fallback." % SO_PATH)
-        _LIB = ctypes.CDLL(SO_PATH)
-        _LIB.lab4d_last_error.restype = ctypes.c_char_p
-        _LIB.lab4d_arch.restype = ctypes.c_char_p
-        _LIB.lab4d_build_flags.restype = ctypes.c_char_p
-        flags = _LIB.lab4d_build_flags().decode().split()
+        so = ctypes.CDLL(SO_PATH)
+        for name, (restype, params, _) in SIGNATURES.items():
+            fn = getattr(so, name)
+            fn.restype, fn.argtypes = restype, argtypes(params)
+        flags = so.lab4d_build_flags().decode().split()
         if flags and os.environ.get("LAB4D_ALLOW_EXPERIMENT_BUILD", "0") != "1":
             # kernel-experiment builds (tools/build_variants.sh) are loaded through LAB4D_SO_PATH by the timing tools only, which set the override
             raise RuntimeError("%s was compiled with kernel-experiment macros %s (most of them give wrong results); rebuild without them, or set "
                                "LAB4D_ALLOW_EXPERIMENT_BUILD=1 for a timing experiment" % (SO_PATH, flags))
-        for name, at in SIGNATURES.items():
-            fn = getattr(_LIB, name)
-            fn.argtypes = at
-            fn.restype = ctypes.c_int64 if name in INT64_RETURNS else ci
+        _LIB = so
     return _LIB if PROF is None else _ProfiledLib(_LIB)
 
 
 class _ProfiledLib:
-    """While per-kernel profiling is on (PROF is a dict): every entry point that is not already inside a `timed` block is timed under its own
-    name, so the per-kernel table of the bench line accounts for ALL of the library's launches, not only the ones with a work model."""
+    """While per-kernel profiling is on (PROF is a dict): every entry point that launches (its prototype has a `stream` parameter) and is not
+    already inside a `timed` block is timed under its own name, so the per-kernel table of the bench line accounts for ALL of the library's
+    launches, not only the ones with a work model."""
 
     def __init__(self, lib_):
         self._lib = lib_
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if PROF is None or _TIMED_DEPTH > 0 or not name.startswith("lab4d_") or name in ("lab4d_last_error", "lab4d_arch", "lab4d_build_flags", "lab4d_mlp_fused_backward_supported", "lab4d_mlp_describe", "lab4d_mlp_packed_bytes", "lab4d_compact_work_ints", "lab4d_global_match_workspace_floats", "lab4d_skin_blend_backward_workspace_floats", "lab4d_mesh_work_ints", "lab4d_mesh_component_work_ints"):  # host-only
+        if PROF is None or _TIMED_DEPTH > 0 or not SIGNATURES.get(name, (None, None, False))[2]:  # no stream parameter: host-only
             return fn
 
         def call(*a):

@@ -23,15 +23,7 @@ from . import quat_utils as Q
 from . import render_utils as RU
 from .warping import composed_warp, dense_warp, skinning_warp, skinning_warp_forward_multi
 
-vp, ci, cf = _lib.vp, _lib.ci, _lib.cf
-_lib.register("lab4d_gauss_density_forward", [vp, vp, ci, vp, ci, vp, vp, vp])
-_lib.register("lab4d_gauss_density_backward", [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp])
-_lib.register("lab4d_l2_normalize_forward", [vp, ci, ci, vp, vp])
-_lib.register("lab4d_l2_normalize_backward", [vp, vp, ci, ci, vp, vp])
-_lib.register("lab4d_flow_cyc_forward", [vp] * 7 + [ctypes.c_long, ci, ci, cf, vp, vp, vp])
-_lib.register("lab4d_flow_cyc_backward", [vp] * 8 + [ctypes.c_long, ci, ci, vp, vp, vp, vp, vp])
-_lib.register("lab4d_volsdf_forward", [vp, vp, ctypes.c_long, vp, vp])
-_lib.register("lab4d_volsdf_backward", [vp, vp, vp, ctypes.c_long, vp, vp, vp])
+vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
 
 def flip_pair(x):
@@ -282,11 +274,6 @@ def compute_feat(P, xyz, prec):
     """FeatureNeRF.compute_feat (feature.py:136-150)."""
     f = mlp.run_chain(mlp.NET_FEAT, prec, P, xyz.reshape(-1, 3), _spf(xyz))
     return L2Normalize.apply(f).view(xyz.shape[:-1] + (16,))
-
-
-_lib.register("lab4d_global_match_workspace_floats", [ctypes.c_int])
-_lib.register("lab4d_global_match_forward", [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3)
-_lib.register("lab4d_global_match_backward", [ctypes.c_void_p] * 7 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 5)
 
 
 class GlobalMatch(Function):
@@ -647,19 +634,19 @@ LOSS_TERMS = ["mask", "feature", "feat_reproj", "rgb", "depth", "flow", "vis", "
               "reg_skin_entropy"]
 
 
+@_lib.mirrors("lab4d_loss_inputs")
 class _LossInputs(ctypes.Structure):
     _fields_ = [(n, vp) for n in ("mask", "feature", "xy_reproj", "rgb", "depth", "flow", "vis", "gauss_mask", "eikonal", "cyc_dist", "delta_skin",
                                   "skin_entropy", "t_mask", "t_feature", "t_hxy", "t_rgb", "t_depth", "t_flow", "t_flow_uct", "t_vis2d", "t_detected",
                                   "balance_wt")] + [("hxy_ld", ci), ("dense_uses_mask", ci), ("mask_all", vp), ("vis_bg", vp), ("vis_bg_wt", cf)]
 
 
+@_lib.mirrors("lab4d_loss_grads")
 class _LossGrads(ctypes.Structure):
     _fields_ = [(n, vp) for n in ("mask", "feature", "xy_reproj", "rgb", "depth", "flow", "vis", "gauss_mask", "eikonal", "cyc_dist", "delta_skin",
                                   "skin_entropy", "mask_all", "vis_bg")]
 
 
-_lib.register("lab4d_ray_losses_forward", [ctypes.POINTER(_LossInputs), ci, ci, ctypes.POINTER(cf * 12), vp, vp, vp])
-_lib.register("lab4d_ray_losses_backward", [ctypes.POINTER(_LossInputs), ci, ci, ctypes.POINTER(cf * 12), vp, vp, ctypes.POINTER(_LossGrads), vp])
 _RENDERED = ("mask", "feature", "xy_reproj", "rgb", "depth", "flow", "vis", "gauss_mask", "eikonal", "cyc_dist", "delta_skin", "skin_entropy")
 _TARGETS = ("t_mask", "t_feature", "t_hxy", "t_rgb", "t_depth", "t_flow", "t_flow_uct", "t_vis2d", "t_detected", "balance_wt")
 

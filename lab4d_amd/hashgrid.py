@@ -10,15 +10,6 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from . import packed  # noqa: F401  (not used here: tests/test_abi.py imports this module, not hashfield, and expects a signature for every declared symbol)
-
-vp, ci = _lib.vp, _lib.ci
-_lib.register("lab4d_hashgrid_forward", [vp, vp, vp, ci, ci, ci, ci, vp, vp])
-_lib.register("lab4d_hashgrid_forward_inside", [vp, vp, vp, ci, ci, ci, ci, vp, vp])
-_lib.register("lab4d_hashgrid_backward", [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp])
-_lib.register("lab4d_hashgrid_absmax", [vp, __import__("ctypes").c_long, vp, vp])
-_lib.register("lab4d_hashgrid_backward_f16", [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp])
-_lib.register("lab4d_hashgrid_flush_f16", [vp, vp, ci, ci, ci, vp, vp])
 
 
 def level_resolutions(L, n_min, n_max):

@@ -32,43 +32,35 @@ PREC_F32, PREC_BF16 = 0, 1
 vp, ci = ctypes.c_void_p, ctypes.c_int
 
 
+@_lib.mirrors("lab4d_mlp_layer")
 class LayerDesc(ctypes.Structure):
     _fields_ = [(n, ci) for n in ("ke", "kin", "mout", "mout_pad", "relu", "pf_bias", "add_ext", "ext_grad")]
 
 
+@_lib.mirrors("lab4d_mlp_desc")
 class NetDesc(ctypes.Structure):
     _fields_ = [(n, ci) for n in ("n_layers", "emb_kind", "n_freq", "c_in", "emb_slots", "ke", "c_out")] + [("layers", LayerDesc * MAXL)]
 
 
+@_lib.mirrors("lab4d_mlp_fwd_args")
 class FwdArgs(ctypes.Structure):
     _fields_ = [("net", ci), ("precision", ci), ("S", ci), ("S_pad", ci), ("ld", ci), ("spf", ci), ("x", vp), ("freq_w", vp),
                 ("W", vp * MAXL), ("bias", vp * MAXL), ("pf_bias", vp * MAXL), ("act", vp * MAXL), ("mask", vp * MAXL), ("emb", vp),
                 ("ext", vp), ("out", vp), ("x2", vp), ("S_dev", vp), ("frame_idx", vp), ("aff", vp)]
 
 
+@_lib.mirrors("lab4d_mlp_bwd_args")
 class BwdArgs(ctypes.Structure):
     _fields_ = [("net", ci), ("precision", ci), ("S", ci), ("S_pad", ci), ("ld", ci), ("spf", ci), ("WT", vp * MAXL), ("act", vp * MAXL),
                 ("mask", vp * MAXL), ("emb", vp), ("ext", vp), ("d_out", vp), ("ext_gin", vp), ("ext_gout", vp), ("dz", vp * MAXL), ("d_x", vp),
                 ("d_x2", vp), ("x", vp), ("aff", vp), ("g_aff", vp)]
 
 
-class BwdFusedArgs(ctypes.Structure):  # lab4d_mlp_bwd_fused_args (include/lab4d_mlp.h)
+@_lib.mirrors("lab4d_mlp_bwd_fused_args")
+class BwdFusedArgs(ctypes.Structure):
     _fields_ = [("net", ci), ("precision", ci), ("S", ci), ("spf", ci), ("x", vp), ("freq_w", vp), ("aff", vp), ("W", vp * MAXL), ("WT", vp * MAXL),
                 ("bias", vp * MAXL), ("pf_bias", vp * MAXL), ("d_out", vp), ("d_x", vp), ("g_aff", vp), ("dW", vp * MAXL), ("db", vp * MAXL),
                 ("pf_db", vp * MAXL)]
-
-
-_lib.register("lab4d_mlp_describe", [ci, ctypes.POINTER(NetDesc)])
-_lib.register("lab4d_mlp_backward_fused", [ctypes.POINTER(BwdFusedArgs), vp])
-_lib.register("lab4d_mlp_fused_backward_supported", [ci, ci, ci])
-_lib.register("lab4d_mlp_pack", [ci, ci, ci, ci, vp, ci, vp, vp, vp])
-_lib.register("lab4d_mlp_forward", [ctypes.POINTER(FwdArgs), vp])
-_lib.register("lab4d_mlp_backward", [ctypes.POINTER(BwdArgs), vp])
-_lib.register("lab4d_mlp_forward_tangent", [ctypes.POINTER(FwdArgs), vp])
-_lib.register("lab4d_eikonal_tangent_input", [vp, vp, vp, vp, ci, ci, ci, vp, vp])
-_lib.register("lab4d_mlp_wgrad", [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp])
-_lib.register("lab4d_mlp_wgrad_mapped", [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp])
-_lib.SIGNATURES["lab4d_mlp_packed_bytes"] = [ci, ci, ci]
 
 
 class NetInfo(NamedTuple):

@@ -6,10 +6,6 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 
-vp, ci = _lib.vp, _lib.ci
-_lib.register("lab4d_compose_order", [vp, ci, vp, ci, ci, vp, vp, vp])
-_lib.register("lab4d_compose_gather", [vp, ci, vp, ci, vp, ci, ci, ci, ci, vp, vp])
-
 
 def compose_order(depth_a, depth_b):
     """argsort of cat([depth_a, depth_b], 2) per ray and its inverse: (M,N,Da,1),(M,N,Db,1) -> int32 (R,Da+Db) x2."""

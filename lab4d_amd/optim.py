@@ -10,12 +10,6 @@ import torch
 
 from . import _lib
 
-vp, ci, cf, i64 = _lib.vp, _lib.ci, _lib.cf, __import__("ctypes").c_int64
-_lib.register("lab4d_grad_norm_clip", [vp, i64, cf, vp, vp, vp, vp])
-_lib.register("lab4d_adamw_step", [vp, vp, vp, vp, i64, vp, vp, ci, cf, cf, cf, cf, ci, vp, vp])
-_lib.register("lab4d_check_grad", [vp, i64, cf, cf, vp, vp, vp, vp, vp, vp])
-_lib.register("lab4d_adamw_step_guarded", [vp, vp, vp, vp, i64, vp, vp, ci, cf, cf, cf, cf, vp, vp, vp, vp])
-
 
 class FlatAdamW:
     """torch.optim.AdamW semantics (decoupled weight decay, bias-corrected moments) with one learning rate per parameter.

@@ -3,7 +3,6 @@ step through the occupied cells of an occgrid.OccupancyGrid and emits the kept s
 (start, count); `composite` renders that list directly.  Nothing of size rays x samples-per-ray exists.  The reference has no counterpart
 (nnutils/nerf.py:98 is a TODO); the rules are written down in the header and in csrc/packed_math.hpp.  Nothing here synchronises with the
 host: every call can be captured in a hipGraph."""
-import ctypes
 import math
 
 import torch
@@ -11,12 +10,6 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-
-vp, ci, cl, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
-_lib.register("lab4d_packed_march_count", [vp, vp, vp, vp, vp, ci, cl, cf, ci, vp, vp])
-_lib.register("lab4d_packed_march_write", [vp, vp, vp, vp, vp, ci, cl, cf, ci, vp, cl] + [vp] * 8 + [vp])
-_lib.register("lab4d_packed_composite_forward", [vp, vp, ctypes.POINTER(_lib.FieldList), vp, vp, cl, cl, vp, vp, vp, vp, vp])
-_lib.register("lab4d_packed_composite_backward", [vp, vp, ctypes.POINTER(_lib.FieldList), vp, vp, cl, cl, vp, vp, vp, vp, ctypes.POINTER(_lib.FieldGrads), vp])
 
 
 def _f32(name, t, *tail):

@@ -24,20 +24,8 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from . import rowmlp  # noqa: F401  (registers the lab4d_rowmlp_* signatures)
+from . import rowmlp
 from .quat_utils import quaternion_mul
-
-vp, ci = _lib.vp, _lib.ci
-_lib.register("lab4d_fk_forward", [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp])
-_lib.register("lab4d_fk_backward", [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp])
-_lib.register("lab4d_skel_bones_forward", [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp])
-_lib.register("lab4d_skel_bones_backward", [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp])
-
-i64_ = __import__("ctypes").c_int64
-_lib.register("lab4d_camera_epilogue_forward", [vp, vp, vp, vp, ci, ci, vp, vp])
-_lib.register("lab4d_camera_epilogue_backward", [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, vp])
-_lib.register("lab4d_intrinsics_epilogue_forward", [vp, vp, vp, vp, vp, ci, ci, vp, vp])
-_lib.register("lab4d_intrinsics_epilogue_backward", [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp])
 
 _SKEL_CACHE = {}
 

@@ -1,8 +1,6 @@
 """Host-side mirror of lab4d/utils/render_utils.py -- same function names and signatures
 (sample_cam_rays, render_pixel, compute_weights, integrate, sample_pdf), executed by the
 gfx950 kernels of liblab4d_hip.so (csrc/raymarch.hip, csrc/composite.hip)."""
-import ctypes
-
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
@@ -321,12 +319,6 @@ def sort_depth(a, b):
 # ---------------------------------------------------------------------------------------------------
 # valid-sample compaction of the evaluation path (include/lab4d_hip.h section 2b; nerf.py:495-528, 769-819)
 # ---------------------------------------------------------------------------------------------------
-_lib.register("lab4d_valid_mask", [_lib.vp] * 4 + [ctypes.c_long, _lib.vp, _lib.vp])
-_lib.register("lab4d_compact", [_lib.vp, ctypes.c_long, _lib.vp, _lib.vp, _lib.vp, _lib.vp])
-_lib.register("lab4d_compact_work_ints", [ctypes.c_long])
-_lib.register("lab4d_gather_rows", [_lib.vp] * 3 + [ctypes.c_long, _lib.ci, _lib.vp, _lib.vp])
-_lib.register("lab4d_scatter_rows", [_lib.vp] * 3 + [ctypes.c_long, _lib.ci, _lib.vp, _lib.vp])
-_lib.register("lab4d_frame_of", [_lib.vp] * 2 + [ctypes.c_long, _lib.ci, _lib.vp, _lib.vp])
 
 
 @torch.no_grad()

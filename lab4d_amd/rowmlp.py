@@ -16,14 +16,16 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 
 MAX_LAYERS = 16
-vp, ci, cf, i32 = _lib.vp, _lib.ci, _lib.cf, ctypes.c_int32
+vp, cf, i32 = ctypes.c_void_p, ctypes.c_float, ctypes.c_int32
 
 
+@_lib.mirrors("lab4d_rowmlp_layer")
 class _Layer(ctypes.Structure):
     _fields_ = [("W", vp), ("b", vp), ("dW", vp), ("db", vp), ("in_dim", i32), ("out_dim", i32), ("src_col", i32), ("dst_col", i32), ("relu", i32),
                 ("acc", i32)]
 
 
+@_lib.mirrors("lab4d_rowmlp_io")
 class _IO(ctypes.Structure):
     _fields_ = [("ptr", vp), ("col", i32), ("width", i32)]
 
@@ -31,14 +33,11 @@ class _IO(ctypes.Structure):
 MAX_IO = 4
 
 
+@_lib.mirrors("lab4d_rowmlp_prog")
 class _Prog(ctypes.Structure):
     _fields_ = [("n_layers", i32), ("row_stride", i32), ("frame_id", vp), ("vstart", vp), ("vidlen", vp), ("vid", vp), ("inst_W", vp), ("d_inst_W", vp),
                 ("max_ts", cf), ("time_scale", cf), ("n_freq", i32), ("four_col", i32), ("inst_col", i32), ("inst_dim", i32), ("inst_rows", i32),
                 ("acc_inst", i32), ("n_in", i32), ("n_out", i32), ("inp", _IO * MAX_IO), ("out", _IO * MAX_IO), ("layer", _Layer * MAX_LAYERS)]
-
-
-_lib.register("lab4d_rowmlp_forward", [ctypes.POINTER(_Prog), vp, ci, vp])
-_lib.register("lab4d_rowmlp_backward", [ctypes.POINTER(_Prog), vp, vp, ci, vp])
 
 
 def _prog(spec, tensors, ins, outs, grads=None, acc=None):

@@ -10,24 +10,13 @@ from torch.autograd.function import once_differentiable
 from . import _lib, mlp
 from . import quat_utils as Q
 
-vp, ci = _lib.vp, _lib.ci
-_lib.register("lab4d_bone_coords_forward", [vp] * 4 + [ci] * 4 + [vp, vp])
-_lib.register("lab4d_bone_coords_backward", [vp] * 5 + [ci] * 4 + [vp] * 4 + [vp])
-_lib.register("lab4d_skin_blend_forward", [vp] * 7 + [ci] * 4 + [vp] * 4 + [vp])
-_lib.register("lab4d_skin_blend_backward", [vp] * 10 + [ci] * 4 + [vp] * 7 + [vp])
-_lib.register("lab4d_skin_blend_backward_acc", [vp] * 10 + [ci] * 4 + [vp] * 7 + [ci, vp])
-_lib.register("lab4d_skin_blend_backward_workspace_floats", [ci] * 5)
-
 
 def _blend_bwd_work(S, spf, M, B, device):
     """Scratch of the blend adjoint, sized by the library (which also decides fused / unfused: one parse of LAB4D_BLEND_FUSE, include/lab4d_skin.h).
     Returns (work, fused)."""
     n = int(_lib.lib().lab4d_skin_blend_backward_workspace_floats(S, spf, M, B, 1))
     return torch.empty(n, device=device), n == M * B * 34
-_lib.register("lab4d_gram_per_frame", [vp, ci, vp, ci, ci, ci, ci, vp, vp])
-_lib.register("lab4d_bone_params_from_gram", [vp] * 4 + [ci] * 2 + [vp] * 3 + [vp])
-_lib.register("lab4d_bone_affine", [vp] * 3 + [ci] * 2 + [vp, vp])
-_lib.register("lab4d_bone_coords_backward_gram", [vp] * 4 + [ci] * 4 + [vp, vp, vp])
+
 
 # The delta-skin chain forms the bone coordinates in its own kernel (SkinChain); 0 restores the two-kernel form (A/B measurements).
 FUSE_BONE_COORDS = os.environ.get("LAB4D_FUSE_BONE", "1") != "0"

@@ -17,7 +17,7 @@ def declared_symbols():
         if not f.endswith(".h"):
             continue
         src = open(os.path.join(ROOT, "include", f)).read()
-        src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+        src = re.sub(r"/\*.*?\*/|//[^\n]*", "", src, flags=re.S)
         names += re.findall(r"\b(lab4d_[a-z0-9_]+)\s*\(", src)
     return sorted(set(names))
 
@@ -35,18 +35,111 @@ def test_library_exports_every_declared_symbol(so):
     assert not missing, missing
 
 
-def test_python_signatures_cover_the_header():
-    import lab4d_amd.deformable  # noqa: F401  (registers the mlp / skinning / gauss-density signatures)
-    import lab4d_amd.mlp  # noqa: F401
-    import lab4d_amd.hashgrid  # noqa: F401
-    import lab4d_amd.ingest  # noqa: F401
-    import lab4d_amd.multifields  # noqa: F401
-    import lab4d_amd.optim  # noqa: F401
-    import lab4d_amd.pose  # noqa: F401
-    import lab4d_amd.warping  # noqa: F401
-    sig = set(_lib.SIGNATURES)
-    hdr = set(declared_symbols()) - {"lab4d_last_error", "lab4d_version", "lab4d_arch", "lab4d_build_flags"}
-    assert hdr <= sig, sorted(hdr - sig)
+def test_parser_skips_no_prototype(so):
+    """The ctypes signatures are parsed from include/*.h (_lib.parse_prototypes): the strict prototype pattern finds exactly the names the loose
+    `lab4d_*(` search above finds -- a prototype the parser cannot read is not silently left without argtypes -- and each resolves in the library."""
+    assert sorted(_lib.SIGNATURES) == declared_symbols()
+    assert not [n for n in _lib.SIGNATURES if not hasattr(so, n)]
+
+
+SMALL_HEADER = """
+/* a block comment that holds int lab4d_x(int a); and spans
+   two lines */
+// a line comment: int lab4d_y(int a);
+typedef struct { int n; } lab4d_t;
+int lab4d_three_lines(const float* x,   /* in */
+                      unsigned char* mask, const int64_t* ids,
+                      int n, void* stream);
+long long lab4d_size(int a, long long b);
+const char* lab4d_name(void);
+int lab4d_takes(const lab4d_t* t, uint32_t k, void* stream);
+"""
+
+
+def test_parser_on_a_small_header():
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    sig = _lib.parse_prototypes(SMALL_HEADER, "small.h")
+    assert sorted(sig) == ["lab4d_name", "lab4d_size", "lab4d_takes", "lab4d_three_lines"]  # nothing from inside the comments
+    assert sig["lab4d_three_lines"] == (ci, [vp, vp, vp, ci, vp], True)
+    assert sig["lab4d_size"] == (ctypes.c_longlong, [ci, ctypes.c_longlong], False)
+    assert sig["lab4d_name"] == (ctypes.c_char_p, [], False)
+    restype, params, has_stream = sig["lab4d_takes"]
+    assert (restype, params, has_stream) == (ci, ["lab4d_t", ctypes.c_uint32, vp], True)
+
+    class T(ctypes.Structure):
+        _fields_ = [("n", ci)]
+    assert _lib.argtypes(params, {}) == [vp, ctypes.c_uint32, vp]  # unbound: a plain pointer, which takes no Structure
+    assert _lib.argtypes(params, {"lab4d_t": T}) == [ctypes.POINTER(T), ctypes.c_uint32, vp]
+    with pytest.raises(TypeError):
+        vp.from_param(T())
+    with pytest.raises(TypeError, match=r"small\.h.*size_t n.*lab4d_bad"):
+        _lib.parse_prototypes("int lab4d_bad(const float* x, size_t n, void* stream);", "small.h")
+    with pytest.raises(TypeError, match=r"small\.h.*double.*lab4d_bad"):
+        _lib.parse_prototypes("double lab4d_bad(void);", "small.h")
+
+
+def test_pinned_signatures():
+    """One signature per feature of the parser, written out by hand."""
+    from lab4d_amd import mlp, packed  # noqa: F401  (mlp binds the mirror of lab4d_mlp_fwd_args)
+    vp, ci, cu, cl, cf, i64, P = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_long, ctypes.c_float, ctypes.c_int64, ctypes.POINTER
+    pinned = {
+        "lab4d_quaternion_mul_forward": (ci, [vp, vp, vp, cu, cu, cu, ci, vp], True),
+        "lab4d_occgrid_mask": (ci, [vp, vp, vp, ci, cl, vp, vp], True),
+        "lab4d_adamw_step": (ci, [vp, vp, vp, vp, i64, vp, vp, ci, cf, cf, cf, cf, ci, vp, vp], True),
+        "lab4d_skin_blend_backward_workspace_floats": (ctypes.c_longlong, [ci] * 5, False),
+        "lab4d_mlp_forward": (ci, [P(mlp.FwdArgs), vp], True),
+        "lab4d_packed_composite_backward": (ci, [vp, vp, P(_lib.FieldList), vp, vp, cl, cl, vp, vp, vp, vp, P(_lib.FieldGrads), vp], True),
+    }
+    for name, want in pinned.items():
+        restype, params, has_stream = _lib.SIGNATURES[name]
+        assert (restype, _lib.argtypes(params), has_stream) == want, name
+
+
+def test_loaded_library_enforces_the_signatures(so):
+    """lib() applies the parsed table to every function: a call one argument short is a TypeError before the library is entered, and a mirror
+    bound after the load reaches the functions already set up."""
+    L = _lib.lib()
+    with pytest.raises(TypeError):
+        L.lab4d_quaternion_conjugate(None, 1, None, 0)
+    assert L.lab4d_last_error.restype is ctypes.c_char_p and list(L.lab4d_version.argtypes) == []
+    old = _lib.MIRRORS["lab4d_field_list"]
+
+    class Other(ctypes.Structure):
+        _fields_ = old._fields_
+    try:
+        _lib.mirrors("lab4d_field_list")(Other)
+        assert L.lab4d_composite_forward.argtypes[2] is ctypes.POINTER(Other)
+    finally:
+        _lib.mirrors("lab4d_field_list")(old)
+    assert L.lab4d_composite_forward.argtypes[2] is L.lab4d_packed_composite_backward.argtypes[2] is ctypes.POINTER(old)
+
+
+def test_data_pointer_parameters_take_host_arrays():
+    """`const float* weights` of lab4d_ray_losses_* and `int* stats` of lab4d_mesh_largest_component are plain pointers (c_void_p): the host arrays
+    their callers pass are accepted, with byref (deformable.RayLosses) and without (mesh.largest_component)."""
+    for name, at in (("lab4d_ray_losses_forward", 3), ("lab4d_ray_losses_backward", 3), ("lab4d_mesh_largest_component", 8)):
+        assert _lib.SIGNATURES[name][1][at] is ctypes.c_void_p
+    w, stats = (ctypes.c_float * 12)(), (ctypes.c_int * 2)()
+    for arg in (w, ctypes.byref(w), stats, None):
+        ctypes.c_void_p.from_param(arg)
+
+
+def test_timed_entry_points_are_the_ones_with_a_stream(so):
+    """_ProfiledLib times a function iff its prototype has a `stream` parameter: no size query, no getter."""
+    timed_names = set()
+    _lib.PROF = {}
+    try:
+        prof = _lib._ProfiledLib(so)
+        for n in _lib.SIGNATURES:
+            if getattr(prof, n) is not getattr(so, n):
+                timed_names.add(n)
+    finally:
+        _lib.PROF = None
+    assert timed_names == {n for n, (_, _, has_stream) in _lib.SIGNATURES.items() if has_stream}
+    host_only = {"lab4d_last_error", "lab4d_arch", "lab4d_build_flags", "lab4d_version", "lab4d_mlp_fused_backward_supported", "lab4d_mlp_describe",
+                 "lab4d_mlp_packed_bytes", "lab4d_compact_work_ints", "lab4d_global_match_workspace_floats",
+                 "lab4d_skin_blend_backward_workspace_floats", "lab4d_mesh_work_ints", "lab4d_mesh_component_work_ints"}
+    assert set(_lib.SIGNATURES) - timed_names == host_only
 
 
 def test_library_targets_gfx950(so):
@@ -165,17 +258,53 @@ def test_rowmlp_programs_are_validated_before_any_launch(so):
     assert so.lab4d_rowmlp_forward(ctypes.byref(p), fake, 4, None) == -1
 
 
-def test_rowmlp_ctypes_structs_have_the_c_layout(tmp_path):
-    """lab4d_amd/rowmlp.py mirrors lab4d_rowmlp_prog / _layer / _io with ctypes.Structure: sizes and the offsets of the arrays must equal what a C compiler
-    gives include/lab4d_rowmlp.h (a field added on one side only would shift every pointer behind it)."""
+def c_struct_fields():
+    """C struct name -> its field names in declaration order, for every `typedef struct {...} lab4d_*;` of include/*.h."""
+    out = {}
+    for f in sorted(os.listdir(os.path.join(ROOT, "include"))):
+        src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", f)).read(), flags=re.S)
+        for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(lab4d_\w+)\s*;", src, flags=re.S):
+            pieces = [p.strip() for decl in body.split(";") for p in decl.split(",")]  # `const float *mask, *feature;` declares two fields
+            out[name] = [re.search(r"(\w+)\s*(\[[^\]]*\])?$", p).group(1) for p in pieces if p]
+    return out
+
+
+def test_ctypes_structs_have_the_c_layout(tmp_path):
+    """Every ctypes.Structure that mirrors a struct of include/*.h (bound with _lib.mirrors: the nine argument structs and the three nested in
+    them) has the layout a C compiler gives the header: the same fields by name in the same order, and for each the same offset and size, and
+    the same total size (a field added on one side only would shift every pointer behind it).  No struct of the headers is left without a mirror."""
     import subprocess
-    from lab4d_amd import rowmlp
+    from lab4d_amd import deformable, mlp, rowmlp
+    py_name = {"in": "inp"}  # `in` is a Python keyword
+    c_fields = c_struct_fields()
+    assert _lib.MIRRORS == {
+        "lab4d_field_list": _lib.FieldList, "lab4d_field_grads": _lib.FieldGrads, "lab4d_mlp_layer": mlp.LayerDesc, "lab4d_mlp_desc": mlp.NetDesc,
+        "lab4d_mlp_fwd_args": mlp.FwdArgs, "lab4d_mlp_bwd_args": mlp.BwdArgs, "lab4d_mlp_bwd_fused_args": mlp.BwdFusedArgs,
+        "lab4d_loss_inputs": deformable._LossInputs, "lab4d_loss_grads": deformable._LossGrads, "lab4d_rowmlp_layer": rowmlp._Layer,
+        "lab4d_rowmlp_io": rowmlp._IO, "lab4d_rowmlp_prog": rowmlp._Prog}
+    assert set(c_fields) == set(_lib.MIRRORS)
+    assert {p for _, params, _ in _lib.SIGNATURES.values() for p in params if isinstance(p, str)} <= set(_lib.MIRRORS)
+    headers = sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
+    lines = []
+    for name, fields in c_fields.items():
+        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        lines += ['printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (name, f, name, f, name, f) for f in fields]
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdint.h>\n#include <stddef.h>\n#include <stdio.h>\n#include "lab4d_rowmlp.h"\n'
-                   'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(lab4d_rowmlp_prog), sizeof(lab4d_rowmlp_layer), sizeof(lab4d_rowmlp_io),'
-                   ' offsetof(lab4d_rowmlp_prog, in), offsetof(lab4d_rowmlp_prog, out), offsetof(lab4d_rowmlp_prog, layer), offsetof(lab4d_rowmlp_prog, max_ts));return 0;}\n')
+    src.write_text("#include <stdint.h>\n#include <stddef.h>\n#include <stdio.h>\n" + "".join('#include "%s"\n' % h for h in headers)
+                   + "int main(void){\n" + "\n".join(lines) + "\nreturn 0;}\n")
     exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    c = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    P = rowmlp._Prog
-    assert c == [ctypes.sizeof(P), ctypes.sizeof(rowmlp._Layer), ctypes.sizeof(rowmlp._IO), P.inp.offset, P.out.offset, P.layer.offset, P.max_ts.offset]
+    subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    c = {}
+    for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines():
+        key, *nums = line.split()
+        c[key] = [int(x) for x in nums]
+    for name, cls in _lib.MIRRORS.items():
+        assert [n for n, _ in cls._fields_] == [py_name.get(f, f) for f in c_fields[name]], name
+        assert c[name] == [ctypes.sizeof(cls)], name
+        for f in c_fields[name]:
+            d = getattr(cls, py_name.get(f, f))
+            assert c[name + "." + f] == [d.offset, d.size], (name, f)
+    # the sizes the entry points' argument structs have today (include/*.h at this commit)
+    assert [c[n][0] for n in ("lab4d_field_list", "lab4d_field_grads", "lab4d_mlp_desc", "lab4d_mlp_fwd_args", "lab4d_mlp_bwd_args",
+                              "lab4d_mlp_bwd_fused_args", "lab4d_loss_inputs", "lab4d_loss_grads", "lab4d_rowmlp_prog")] == \
+        [264, 136, 412, 576, 488, 736, 208, 112, 1120]

@@ -421,6 +421,24 @@ def test_stream_compaction_matches_nonzero(S, p):
     assert torch.equal(fr[: ref.numel()], ref // 7) and int(fr[ref.numel():].abs().sum()) == 0
 
 
+def test_profile_times_the_launch_and_not_the_size_query():
+    """Per-kernel profiling (_lib.PROF) times the entry points whose prototype has a `stream` parameter: the compaction launch gets an entry,
+    the host-only size query it is sized with (lab4d_compact_work_ints) does not."""
+    from lab4d_amd import _lib, render_utils as RU
+    mask = (torch.rand(256, generator=gen(77)) < 0.5).to(torch.uint8)
+    _lib.PROF = {}
+    try:
+        assert int(_lib.lib().lab4d_compact_work_ints(256)) > 0
+        idx, count = RU.compact(mask.to(DEV))
+        torch.cuda.synchronize()
+        prof = _lib.prof_summary()
+    finally:
+        _lib.PROF = None
+    assert prof["compact"][0] == 1, prof
+    assert not [k for k in prof if "work_ints" in k], prof
+    assert int(count) == int(mask.sum()) and torch.equal(idx.cpu()[: int(count)], torch.nonzero(mask).flatten().int())
+
+
 def test_valid_mask_is_bit_exact_at_the_box_faces():
     """check_inside_aabb uses strict inequalities (geom_utils.py:506-517): points exactly on a face are outside."""
     from lab4d_amd import render_utils as RU
