@@ -277,6 +277,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_packed.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 14. Signed distance from points to a triangle mesh -- nnutils/nerf.py:217-230 (NeRF.get_init_sdf_fn: pysdf; the
+ *     rules are this repository's own, parity unpinned).  See lab4d_meshsdf.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_meshsdf.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ fixtures).
 """
 import math
 import sys
+import types
 from collections import defaultdict
 
 import torch
@@ -57,14 +58,26 @@ N_DEPTH = 64
 _PREC_NAMES = {"bf16": mlp.PREC_BF16, "f32": mlp.PREC_F32}
 
 
-def configure(module, precision=None, n_depth=None, mesher=None):
+def configure(module, precision=None, n_depth=None, mesher=None, init_sdf=None):
     """Per-model settings: every sub-module of `module` (a dvr_model, a MultiFields, one field, one warp ...) runs its kernels at this
     precision ("bf16" / "f32") / with this many samples per ray, whatever the process-wide defaults of patch() are.
     mesher="device": NeRF.extract_canonical_mesh extracts the iso-surface with lab4d_amd.mesh (no skimage / trimesh needed) instead of
-    handing the volumes to the reference's geom_utils.marching_cubes; mesher="reference" switches back.  Default: the reference's."""
+    handing the volumes to the reference's geom_utils.marching_cubes; mesher="reference" switches back.  Default: the reference's.
+    init_sdf="device": `get_init_sdf_fn()` of every field that has the method or whose `proxy_geometry` carries .vertices / .faces answers
+    with lab4d_amd.proxy.init_sdf_fn (the mesh distance on the device, no pysdf needed) instead of building a pysdf.SDF on the host;
+    init_sdf="reference" removes that binding again.  Default: the reference's own method.  The binding lives on the module object, so
+    the class -- and with it every other model in the process -- keeps the reference's."""
     if mesher not in (None, "device", "reference"):
         raise ValueError("lab4d_amd.patch.configure: mesher must be 'device' or 'reference', got %r" % (mesher,))
+    if init_sdf not in (None, "device", "reference"):
+        raise ValueError("lab4d_amd.patch.configure: init_sdf must be 'device' or 'reference', got %r" % (init_sdf,))
     for m in module.modules():
+        if init_sdf is not None:
+            m._lab4d_amd_init_sdf = init_sdf
+            m.__dict__.pop("get_init_sdf_fn", None)
+            geom = getattr(m, "proxy_geometry", None)
+            if init_sdf == "device" and (hasattr(type(m), "get_init_sdf_fn") or (hasattr(geom, "vertices") and hasattr(geom, "faces"))):
+                m.__dict__["get_init_sdf_fn"] = types.MethodType(nerf_get_init_sdf_fn, m)
         if mesher is not None:
             m._lab4d_amd_mesher = mesher
         if precision is not None:
@@ -604,6 +617,16 @@ def nerf_extract_canonical_mesh(self, grid_size=64, level=0.0, inst_id=None, use
         return f
     return geom.marching_cubes(served(sdf), box, visibility_func=served(vis) if use_visibility else None, grid_size=grid_size, level=level,
                                apply_connected_component=True if self.category == "fg" else False)
+
+
+def nerf_get_init_sdf_fn(self):
+    """NeRF.get_init_sdf_fn (nnutils/nerf.py:217-230) with configure(field, init_sdf="device"): `pts (N,3) -> sdf (N,1)`, negative inside,
+    from self.proxy_geometry's .vertices / .faces through lab4d_amd.proxy.init_sdf_fn -- the distance is computed where the points are."""
+    from . import proxy
+    geom = getattr(self, "proxy_geometry", None)
+    if not (hasattr(geom, "vertices") and hasattr(geom, "faces")):
+        raise RuntimeError("lab4d_amd.patch: init_sdf='device' needs a proxy_geometry with .vertices and .faces, got %s" % type(geom).__name__)
+    return proxy.init_sdf_fn(geom.vertices, geom.faces)
 
 
 def nerf_update_aabb(self, beta=0.9):

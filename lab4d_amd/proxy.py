@@ -12,6 +12,7 @@ import torch
 
 from . import deformable as DF
 from . import mesh as _mesh
+from . import meshsdf as _meshsdf
 from . import mlp
 from . import quat_utils as Q
 
@@ -73,6 +74,28 @@ def extract_mesh(P, aabb, grid_size=64, level=0.0, code_base=None, code_vis=None
                                         largest_component=largest_component)
     bounds = torch.stack([verts.min(0)[0], verts.max(0)[0]], 0) if verts.shape[0] else None
     return verts, faces, bounds
+
+
+def init_sdf_fn(verts, faces):
+    """NeRF.get_init_sdf_fn (nerf.py:217-230) on the device: from a mesh (vertices (V,3), faces (F,3); tensors, or the numpy arrays of a
+    trimesh.Trimesh / lab4d_amd.mesh.Mesh) the callable `pts (N,3) -> sdf (N,1)`, negative inside, that geometry_init fits the field to
+    (nerf.py:251-295).  The reference builds a pysdf.SDF on the host and copies every batch of points there and back; here the mesh is
+    moved to the points' device once and lab4d_amd.meshsdf.signed_distance answers in place."""
+    cache = {}
+
+    def mesh_on(device):
+        if device not in cache:
+            v = torch.as_tensor(verts).detach().to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
+            f = torch.as_tensor(faces).detach().to(device=device, dtype=torch.int32).reshape(-1, 3).contiguous()
+            cache[device] = (v, f)
+        return cache[device]
+
+    def sdf_fn(pts):
+        v, f = mesh_on(pts.device)
+        sdf = _meshsdf.signed_distance(v, f, pts.detach().to(torch.float32).contiguous())
+        return sdf[..., None].to(pts.dtype)
+
+    return sdf_fn
 
 
 def grid_to_world(verts01, box):
