@@ -283,6 +283,13 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_meshsdf.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 15. The hash field's SDF with its gradient in the point, and the adjoint of both: eikonal term and normals of the hash field
+ *     (nnutils/nerf.py:416-493 for the positional-encoding fields; not in the reference for a hash field, parity unpinned).
+ *     See lab4d_hashsdf.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_hashsdf.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,12 +16,17 @@ field's density with update_occupancy() and handed to forward_compacted(occ=...)
 grid.ray_depths() places a ray's samples between its first and last occupied cell.  render_packed() goes all the way: the rays are marched at a
 fixed step through the occupied cells only (packed.march), the field runs on the packed list of kept samples, and the list is composited per ray
 (packed.composite); nothing of size rays x samples-per-ray exists.  All of it is opt-in.
+
+The SDF as an SDF: sdf_gradient() returns the sdf with its gradient in the point from one fused kernel (hashsdf.py, include/lab4d_hashsdf.h),
+differentiable in the table and the geometry net; eikonal_loss() and normals() build on it (the counterparts of nnutils/nerf.py:416-493), and
+render_packed(with_normal=True) composites a normal map.  Opt-in as well.
 """
 import math
 
 import torch
+import torch.nn.functional as F
 
-from . import hashgrid, mlp, packed
+from . import hashgrid, hashsdf, mlp, packed
 from . import render_utils as RU
 from .deformable import volsdf_density
 
@@ -118,15 +123,59 @@ def forward_compacted(P, cfg, xyz, dirs, cap, prec=mlp.PREC_F32, res=None, get_d
     return RU.scatter_rows_ad(rgb_c, idx, count, S), RU.scatter_rows_ad(d_c, idx, count, S), count, overflow
 
 
-def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None):
+def sdf_gradient(P, cfg, xyz, res=None, work_rows=None):
+    """xyz (S,3) in the field's frame (must not require grad) -> sdf (S,1), grad (S,3) = d sdf / d xyz = grad01 / (hi - lo), from ONE fused
+    kernel (csrc/hashsdf.hip): the encoding, the geometry net 32 -> 64, ReLU -> row 0 of the head, and the chain rule through both.  What
+    compute_gradient(fn, x) gives the positional-encoding fields (utils/torch_utils.py:4-27, nnutils/nerf.py:437).  The derivative is the
+    one of the grid cell the point lies in.  Outside the box grad = 0 and sdf is what forward(get_density=False) returns there.  Both
+    outputs are differentiable (once) in hash.table, hash.geo.0.* and hash.geo.2.*, whose rows 1..15 get exact zeros; there is no
+    gradient to the points.  work_rows: see hashsdf.sdf_grad01."""
+    if cfg["L"] * cfg["F"] != 32:
+        raise NotImplementedError("hash field: the geometry net is instantiated for L*F = 32 hash features")
+    if xyz.requires_grad:
+        raise RuntimeError("hashfield.sdf_gradient: xyz must not require grad: second derivatives in the points are not implemented (pass xyz.detach())")
+    lo, hi = P["aabb"][0], P["aabb"][1]
+    x01 = (xyz - lo) / (hi - lo)
+    if res is None:
+        res = resolutions(cfg, xyz.device)
+    sdf, g01 = hashsdf.sdf_grad01(x01, P["hash.table"], res, cfg["log2_T"], P["hash.geo.0.weight"], P["hash.geo.0.bias"], P["hash.geo.2.weight"][0],
+                                  P["hash.geo.2.bias"][:1], work_rows=work_rows)
+    return sdf[:, None], g01 / (hi - lo)
+
+
+def eikonal_loss(P, cfg, xyz, res=None, work_rows=None):
+    """(|grad sdf| - 1)^2 per point, (S,1): the form of nnutils/nerf.py:451,486, times the inside mask (a point outside the box has no
+    geometry to regularise).  Where grad == 0 the norm's derivative is torch's (zero).  Gradients as in sdf_gradient."""
+    lo, hi = P["aabb"][0], P["aabb"][1]
+    x01 = (xyz - lo) / (hi - lo)
+    inside = ((x01 >= 0) & (x01 <= 1)).all(-1, keepdim=True).to(torch.float32)
+    _, grad = sdf_gradient(P, cfg, xyz, res=res, work_rows=work_rows)
+    return (grad.norm(2, -1, keepdim=True) - 1) ** 2 * inside
+
+
+@torch.no_grad()
+def normals(P, cfg, xyz, res=None):
+    """Unit normals (S,3) in the field's frame: F.normalize(grad sdf); zero where the gradient is zero (outside the box).  No gradients.
+    The reference flips the sign of its normals towards the camera (the ECON convention of nnutils/nerf.py:489-491: a multiplication by [1, -1, -1]): that flip belongs to
+    camera space, where the view direction is known, and is NOT applied here."""
+    return F.normalize(sdf_gradient(P, cfg, xyz.detach(), res=res)[1], dim=-1)
+
+
+def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None, with_normal=False):
     """Renders rays through the hash field with packed marching (include/lab4d_packed.h): packed.march(grid, origin, dir, t_range, dt, cap, k_max)
     keeps the candidates t0 + (k + 0.5) dt of every ray whose cell's bit is set -- what forward_compacted(occ=grid) keeps of the same lattice --
     as one packed list of at most `cap` rows (STATIC: the call is capturable), forward() runs on those rows (the parked rows behind the count lie
     outside the box: zero encoding, masked), and packed.composite renders colour and depth per ray with delta = dt * |dir|.  origin, dir (R,3) in the
     field's frame, t_range (R,2).  Returns (rgb (R,3), mask (R,1), depth (R,1), total (1,) int32 = kept samples before the capacity, overflow (1,) bool =
     total > cap: samples were dropped, callers check it where they synchronise anyway).  A ray without a kept sample renders zeros.  Gradients flow
-    to the table, the Linears and logibeta."""
+    to the table, the Linears and logibeta.
+    with_normal=True: normals() of the kept rows is composited like the colour and `normal (R,3)` is appended to the returned tuple (the
+    weighted mean of unit normals: not renormalised; gradients reach it through the weights only).  The other five are unchanged."""
     rays = packed.march(grid, origin, dir, t_range, dt, cap, k_max=k_max)
     rgb_s, dens_s = forward(P, cfg, rays.xyz, rays.dirs, spf=max(int(cap), 1), prec=prec, res=res, table_grad_f16=table_grad_f16)
-    rendered, mask = packed.composite(dens_s, rays.deltas, {"rgb": rgb_s, "depth": rays.t[:, None]}, rays)
-    return rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow
+    fields = {"rgb": rgb_s, "depth": rays.t[:, None]}
+    if with_normal:
+        fields["normal"] = normals(P, cfg, rays.xyz, res=res)
+    rendered, mask = packed.composite(dens_s, rays.deltas, fields, rays)
+    out = (rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow)
+    return out + (rendered["normal"],) if with_normal else out
