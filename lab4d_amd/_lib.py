@@ -111,14 +111,18 @@ _RETURNS = {"int": ci, "long": ctypes.c_long, "int64_t": ctypes.c_int64, "long l
 _PROTOTYPE = re.compile(r"^[ \t]*([A-Za-z_][\w \t*]*?)\s*\b(lab4d_\w+)\s*\(([^()]*)\)\s*;", re.M)
 
 
+def _declarations(text):
+    """(return type, name, parameter text, the prototype on one line) of every `<return type> lab4d_<name>(<params>);` outside the comments."""
+    for ret, name, params in _PROTOTYPE.findall(re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)):
+        yield ret, name, params, "%s %s(%s)" % (ret.strip(), name, " ".join(params.split()))
+
+
 def parse_prototypes(text, where):
     """C header text -> {name: (restype, params, has_stream)} for every `<return type> lab4d_<name>(<params>);` in it.  A parameter is a ctypes
     scalar type, c_void_p for a data pointer, or the C NAME of a lab4d_* struct for a pointer to one (argtypes() gives it its type).  A type
     outside the closed maps above raises: there is no default."""
-    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     out = {}
-    for ret, name, params in _PROTOTYPE.findall(text):
-        proto = "%s %s(%s)" % (ret.strip(), name, " ".join(params.split()))
+    for ret, name, params, proto in _declarations(text):
         ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
         if ret not in _RETURNS:
             raise TypeError("%s: return type '%s' of `%s` is not one of %s" % (where, ret, proto, sorted(_RETURNS)))
@@ -285,6 +289,70 @@ def require_device(*tensors):
             raise RuntimeError("lab4d_amd ops need device (HIP) tensors; got a %s tensor -- there is no CPU path" % t.device)
         if not t.is_contiguous():
             raise RuntimeError("lab4d_amd ops need contiguous tensors")
+
+
+def prototype(full):
+    """The C prototype of an entry point on one line, as include/*.h declares it (for error messages)."""
+    for h in sorted(os.listdir(INCLUDE)):
+        if h.endswith(".h"):
+            with open(os.path.join(INCLUDE, h)) as fh:
+                for _, name, _, proto in _declarations(fh.read()):
+                    if name == full:
+                        return proto
+
+
+_BYREF = type(ctypes.byref(ci()))
+_STRUCT_POINTERS = (ctypes._Pointer, _BYREF)
+_DATA_POINTERS = (vp, ctypes.Array) + _STRUCT_POINTERS  # what a data-pointer slot takes beside None and a tensor
+
+
+def marshal(name, args):
+    """The ctypes-ready values of `args` for the entry point lab4d_<name>, each held against its slot of the parsed prototype (the stream is not
+    among them).  A data pointer takes None, a contiguous device tensor or a ctypes pointer/array -- never a number, which c_void_p would pass
+    on as an address; a struct pointer takes None, the bound mirror or a byref/pointer; an integer slot an int; a float slot an int or a float.
+    Decided by include/*.h alone: the library is not touched."""
+    full = "lab4d_" + name
+    if full not in SIGNATURES:
+        raise RuntimeError("include/*.h declares no entry point %s" % full)
+    _, params, has_stream = SIGNATURES[full]
+    if len(args) != len(params) - has_stream:
+        raise TypeError("%s takes %d arguments%s, got %d: `%s`"
+                        % (full, len(params) - has_stream, " before the stream" if has_stream else "", len(args), prototype(full)))
+
+    def refuse(i, wants):
+        got = "a %s tensor" % str(args[i].dtype).replace("torch.", "") if isinstance(args[i], torch.Tensor) else repr(args[i])
+        return TypeError("%s: args[%d] must be %s, got %s: `%s`" % (full, i, wants, got, prototype(full)))
+
+    out = []
+    for i, (p, a) in enumerate(zip(params, args)):
+        if p is vp:
+            if isinstance(a, torch.Tensor):
+                if not (a.is_cuda and a.is_contiguous()):
+                    require_device(a)  # (raises; not called on the good path: it costs as much as the rest of the slot)
+                a = ptr(a)
+            elif a is not None and not isinstance(a, _DATA_POINTERS):
+                raise refuse(i, "a data pointer (None, a device tensor or a ctypes pointer)")
+        elif isinstance(p, str):
+            if isinstance(a, MIRRORS.get(p, ())):
+                a = ctypes.byref(a)
+            elif a is not None and not isinstance(a, _STRUCT_POINTERS):
+                raise refuse(i, "a pointer to %s (None, its ctypes mirror or a byref of one)" % p)
+        elif p is ctypes.c_float:
+            if not isinstance(a, (int, float)):
+                raise refuse(i, "a number")
+        elif not isinstance(a, int):
+            raise refuse(i, "an int")
+        out.append(a)
+    return out
+
+
+def call(name, *args, what=None):
+    """Launch the status-returning entry point lab4d_<name>: marshal() the arguments, add torch's current stream where the prototype has one,
+    and raise on a non-zero status (labelled `what`, by default the name)."""
+    a = marshal(name, args)
+    if SIGNATURES["lab4d_" + name][2]:
+        a.append(stream())
+    check(getattr(lib(), "lab4d_" + name)(*a), what or name)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -73,8 +73,7 @@ class GaussDensity(Function):
         out = torch.empty(S, 1, device=xyz.device)
         best = torch.empty(S, dtype=torch.int32, device=xyz.device)
         ib = ibeta.detach().reshape(1).float().contiguous()  # stays on the device: no host sync (graph-capturable)
-        _lib.check(_lib.lib().lab4d_gauss_density_forward(_lib.ptr(xyz), _lib.ptr(centres), B, _lib.ptr(ib), S, _lib.ptr(out), _lib.ptr(best),
-                                                          _lib.stream()), "gauss_density_forward")
+        _lib.call("gauss_density_forward", xyz, centres, B, ib, S, out, best)
         ctx.save_for_backward(xyz, centres, best, ib)
         return out
 
@@ -86,9 +85,7 @@ class GaussDensity(Function):
         gx = torch.empty_like(xyz)
         gc = torch.zeros_like(centres)
         gi = torch.zeros(1, device=xyz.device)
-        _lib.check(_lib.lib().lab4d_gauss_density_backward(_lib.ptr(xyz), _lib.ptr(centres), centres.shape[0], _lib.ptr(ib), _lib.ptr(best), _lib.ptr(g),
-                                                           xyz.shape[0], _lib.ptr(gx), _lib.ptr(gc), _lib.ptr(gi), _lib.stream()),
-                   "gauss_density_backward")
+        _lib.call("gauss_density_backward", xyz, centres, centres.shape[0], ib, best, g, xyz.shape[0], gx, gc, gi)
         return gx, gc, gi
 
 
@@ -124,9 +121,7 @@ class FlowCyc(Function):
         S = M * N * D
         flow = torch.empty(M, N, D, 3, device=xyz_next.device)
         cyc = torch.empty(M, N, D, 1, device=xyz_next.device) if has_cyc else None
-        _lib.check(_lib.lib().lab4d_flow_cyc_forward(_lib.ptr(xyz_next), _lib.ptr(q), _lib.ptr(t), _lib.ptr(Kmat), _lib.ptr(hxy), _lib.ptr(xyz_cyc),
-                                                     _lib.ptr(xyz_t), S, N * D, D, -1.0 if flow_thresh is None else float(flow_thresh), _lib.ptr(flow),
-                                                     _lib.ptr(cyc), _lib.stream()), "flow_cyc_forward")
+        _lib.call("flow_cyc_forward", xyz_next, q, t, Kmat, hxy, xyz_cyc, xyz_t, S, N * D, D, -1.0 if flow_thresh is None else float(flow_thresh), flow, cyc)
         ctx.save_for_backward(xyz_next, q, t, Kmat, xyz_cyc, xyz_t)
         ctx.dims = (M, N, D)
         return (flow, cyc) if has_cyc else (flow, None)
@@ -145,9 +140,7 @@ class FlowCyc(Function):
         g_pf = torch.empty(M, 16, device=g_flow.device)
         g_xc = torch.empty_like(xyz_cyc) if has_cyc else None
         g_xt = torch.empty_like(xyz_t) if has_cyc else None
-        _lib.check(_lib.lib().lab4d_flow_cyc_backward(_lib.ptr(xyz_next), _lib.ptr(q), _lib.ptr(t), _lib.ptr(Kmat), _lib.ptr(xyz_cyc), _lib.ptr(xyz_t),
-                                                      _lib.ptr(g_flow), _lib.ptr(g_cyc) if has_cyc else None, S, N * D, M, _lib.ptr(g_next), _lib.ptr(g_pf),
-                                                      _lib.ptr(g_xc), _lib.ptr(g_xt), _lib.stream()), "flow_cyc_backward")
+        _lib.call("flow_cyc_backward", xyz_next, q, t, Kmat, xyz_cyc, xyz_t, g_flow, g_cyc if has_cyc else None, S, N * D, M, g_next, g_pf, g_xc, g_xt)
         return g_next, g_pf[:, :4], g_pf[:, 4:7], g_pf[:, 7:].reshape(M, 3, 3), None, g_xc, g_xt, None
 
 
@@ -159,7 +152,7 @@ class VolSdfDensity(Function):
         sdf_c, ib = sdf.contiguous().float(), ibeta.reshape(1).contiguous().float()
         _lib.require_device(sdf_c, ib)
         out = torch.empty_like(sdf_c)
-        _lib.check(_lib.lib().lab4d_volsdf_forward(_lib.ptr(sdf_c), _lib.ptr(ib), sdf_c.numel(), _lib.ptr(out), _lib.stream()), "volsdf_forward")
+        _lib.call("volsdf_forward", sdf_c, ib, sdf_c.numel(), out)
         ctx.save_for_backward(sdf_c, ib)
         ctx.ib_shape = ibeta.shape
         return out
@@ -171,8 +164,7 @@ class VolSdfDensity(Function):
         g = g.contiguous()
         g_sdf = torch.empty_like(sdf)
         g_ib = torch.empty(1, device=sdf.device) if ctx.needs_input_grad[1] else None
-        _lib.check(_lib.lib().lab4d_volsdf_backward(_lib.ptr(sdf), _lib.ptr(ib), _lib.ptr(g), sdf.numel(), _lib.ptr(g_sdf), _lib.ptr(g_ib), _lib.stream()),
-                   "volsdf_backward")
+        _lib.call("volsdf_backward", sdf, ib, g, sdf.numel(), g_sdf, g_ib)
         return g_sdf, None if g_ib is None else g_ib.view(ctx.ib_shape)
 
 
@@ -255,7 +247,7 @@ class L2Normalize(Function):
         _lib.require_device(x)
         S, C = x.shape
         y = torch.empty_like(x)
-        _lib.check(_lib.lib().lab4d_l2_normalize_forward(_lib.ptr(x), S, C, _lib.ptr(y), _lib.stream()), "l2_normalize_forward")
+        _lib.call("l2_normalize_forward", x, S, C, y)
         ctx.save_for_backward(x)
         return y
 
@@ -265,8 +257,7 @@ class L2Normalize(Function):
         (x,) = ctx.saved_tensors
         g = g.contiguous()
         gx = torch.empty_like(x)
-        _lib.check(_lib.lib().lab4d_l2_normalize_backward(_lib.ptr(x), _lib.ptr(g), x.shape[0], x.shape[1], _lib.ptr(gx), _lib.stream()),
-                   "l2_normalize_backward")
+        _lib.call("l2_normalize_backward", x, g, x.shape[0], x.shape[1], gx)
         return gx
 
 
@@ -289,8 +280,7 @@ class GlobalMatch(Function):
         out = torch.empty(R, 3, device=feat_px.device)
         stats = torch.empty(R, 2, device=feat_px.device)
         with _lib.timed("k_match_fwd", (2.0 * R * K * (C + 3), 4.0 * (R * (C + 5) + K * (C + 3)))):
-            _lib.check(_lib.lib().lab4d_global_match_forward(_lib.ptr(feat_px), _lib.ptr(feat_c), _lib.ptr(xyz_c), _lib.ptr(logsigma), R, C, K,
-                                                             _lib.ptr(out), _lib.ptr(stats), _lib.stream()), "global_match_forward")
+            _lib.call("global_match_forward", feat_px, feat_c, xyz_c, logsigma, R, C, K, out, stats)
         ctx.save_for_backward(feat_px, feat_c, xyz_c, logsigma, out, stats)
         return out
 
@@ -306,9 +296,7 @@ class GlobalMatch(Function):
         g_fc, g_xc, g_ls = torch.empty_like(feat_c), torch.empty_like(xyz_c), torch.empty_like(logsigma)
         work = torch.empty(_lib.lib().lab4d_global_match_workspace_floats(K), device=g.device)
         with _lib.timed("k_match_bwd", (2.0 * R * K * (2 * C + 8), 4.0 * (R * (C + 8) + 2 * K * (C + 3)))):
-            _lib.check(_lib.lib().lab4d_global_match_backward(_lib.ptr(feat_px), _lib.ptr(feat_c), _lib.ptr(xyz_c), _lib.ptr(logsigma), _lib.ptr(out),
-                                                              _lib.ptr(stats), _lib.ptr(g), R, C, K, _lib.ptr(g_fc), _lib.ptr(g_xc), _lib.ptr(g_ls),
-                                                              _lib.ptr(work), _lib.stream()), "global_match_backward")
+            _lib.call("global_match_backward", feat_px, feat_c, xyz_c, logsigma, out, stats, g, R, C, K, g_fc, g_xc, g_ls, work)
         return None, g_fc, g_xc, g_ls
 
 
@@ -681,8 +669,7 @@ class RayLosses(Function):
         w = (cf * 12)(*[float(x) for x in weights])
         acc = torch.empty(24, device=ref.device)
         loss = torch.empty(13, device=ref.device)
-        _lib.check(_lib.lib().lab4d_ray_losses_forward(ctypes.byref(a), R, int(N), ctypes.byref(w), _lib.ptr(acc), _lib.ptr(loss), _lib.stream()),
-                   "ray_losses_forward")
+        _lib.call("ray_losses_forward", ctypes.byref(a), R, int(N), ctypes.byref(w), acc, loss)
         ctx.keep = (rendered, targets, extras, acc, [float(x) for x in weights], R, int(N), hxy_ld)
         ctx.shapes = [None if t is None else t.shape for t in tensors[:12]] + [None if t is None else t.shape for t in tensors[22:24]]
         return loss
@@ -704,8 +691,7 @@ class RayLosses(Function):
             outs.append(o)
             setattr(gr, n, None if o is None else _lib.dp(o))
         w = (cf * 12)(*weights)
-        _lib.check(_lib.lib().lab4d_ray_losses_backward(ctypes.byref(a), R, N, ctypes.byref(w), _lib.ptr(acc), _lib.ptr(g_loss), ctypes.byref(gr),
-                                                        _lib.stream()), "ray_losses_backward")
+        _lib.call("ray_losses_backward", ctypes.byref(a), R, N, ctypes.byref(w), acc, g_loss, ctypes.byref(gr))
         gs = [None if o is None else o.view(sh) for o, sh in zip(outs, ctx.shapes)]
         return (None, None) + tuple(gs[:12]) + (None,) * 10 + tuple(gs[12:])
 

@@ -41,8 +41,7 @@ class _HashEncode(Function):
         out = torch.empty(S, L * F, device=x.device)
         # algorithmic bytes: 8 vertices x F floats gathered per level, the point read, L*F floats written
         with _lib.timed("k_hashgrid_fwd", (0.0, 4.0 * S * (8 * L * F + 3 + L * F))):
-            fn = _lib.lib().lab4d_hashgrid_forward_inside if inside_only else _lib.lib().lab4d_hashgrid_forward
-            _lib.check(fn(_lib.ptr(x), _lib.ptr(table), _lib.ptr(res), S, L, log2_T, F, _lib.ptr(out), _lib.stream()), "hashgrid_forward")
+            _lib.call("hashgrid_forward_inside" if inside_only else "hashgrid_forward", x, table, res, S, L, log2_T, F, out)
         ctx.save_for_backward(x, table, res)
         ctx.log2_T, ctx.f16_from = log2_T, f16_from
         return out
@@ -66,17 +65,13 @@ class _HashEncode(Function):
                 _G16[key] = (torch.zeros(L << ctx.log2_T, dtype=torch.int32, device=x.device), torch.zeros(1, dtype=torch.int32, device=x.device))
             g16, amax = _G16[key]
             amax.zero_()
-            lib = _lib.lib()
             with _lib.timed("k_hashgrid_bwd", (0.0, 4.0 * S * (2 * 8 * L * F + 6 + L * F))):
-                _lib.check(lib.lab4d_hashgrid_absmax(_lib.ptr(g), g.numel(), _lib.ptr(amax), _lib.stream()), "hashgrid_absmax")
-                _lib.check(lib.lab4d_hashgrid_backward_f16(_lib.ptr(x), _lib.ptr(table), _lib.ptr(res), _lib.ptr(g), S, L, ctx.log2_T, int(ctx.f16_from),
-                                                           _lib.ptr(g_table), _lib.ptr(g16), _lib.ptr(amax), _lib.ptr(g_x), _lib.stream()), "hashgrid_backward_f16")
-                _lib.check(lib.lab4d_hashgrid_flush_f16(_lib.ptr(g16), _lib.ptr(amax), L, ctx.log2_T, int(ctx.f16_from), _lib.ptr(g_table), _lib.stream()),
-                           "hashgrid_flush_f16")
+                _lib.call("hashgrid_absmax", g, g.numel(), amax)
+                _lib.call("hashgrid_backward_f16", x, table, res, g, S, L, ctx.log2_T, int(ctx.f16_from), g_table, g16, amax, g_x)
+                _lib.call("hashgrid_flush_f16", g16, amax, L, ctx.log2_T, int(ctx.f16_from), g_table)
             return g_x, g_table, None, None, None, None
         with _lib.timed("k_hashgrid_bwd", (0.0, 4.0 * S * (2 * 8 * L * F + 6 + L * F))):  # vertices read (d/dx) and atomically added to
-            _lib.check(_lib.lib().lab4d_hashgrid_backward(_lib.ptr(x), _lib.ptr(table), _lib.ptr(res), _lib.ptr(g), S, L, ctx.log2_T, F, _lib.ptr(g_table),
-                                                          _lib.ptr(g_x), _lib.stream()), "hashgrid_backward")
+            _lib.call("hashgrid_backward", x, table, res, g, S, L, ctx.log2_T, F, g_table, g_x)
         return g_x, g_table, None, None, None, None
 
 

@@ -59,9 +59,7 @@ def _check(x01, table, res, log2_T, W1, b1, w2, b2, work_rows):
             raise RuntimeError("lab4d_amd.hashsdf: %s must be float32 %s, got %s %s" % (name, shape, t.dtype, tuple(t.shape)))
     if work_rows is not None and not 1 <= int(work_rows) <= MAX_ROWS:
         raise RuntimeError("lab4d_amd.hashsdf: work_rows = %d outside [1, %d]" % (int(work_rows), MAX_ROWS))
-    for t in (x01, table, res, W1, b1, w2, b2):
-        if not t.is_cuda:
-            raise RuntimeError("lab4d_amd ops need device (HIP) tensors; got a %s tensor -- there is no CPU path" % t.device)
+    _lib.require_device(x01, table, res, W1, b1, w2, b2)
 
 
 class _HashSdf(Function):
@@ -75,8 +73,7 @@ class _HashSdf(Function):
         grad01 = torch.empty(S, 3, dtype=torch.float32, device=x01.device)
         # algorithmic bytes: the table gathered twice (8 vertices x F floats per level), the point read, 4 floats written
         with _lib.timed("k_hashsdf_fwd", (2.0 * S * (2 * HID * ENC), 4.0 * S * (2 * 8 * L * F + 3 + 4))):
-            _lib.check(_lib.lib().lab4d_hashsdf_forward(_lib.ptr(x01), _lib.ptr(table), _lib.ptr(res), S, L, log2_T, F, _lib.ptr(W1), _lib.ptr(b1),
-                                                        _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(sdf), _lib.ptr(grad01), _lib.stream()), "hashsdf_forward")
+            _lib.call("hashsdf_forward", x01, table, res, S, L, log2_T, F, W1, b1, w2, b2, sdf, grad01)
         ctx.save_for_backward(x01, table, res, W1, b1, w2, b2)
         ctx.log2_T, ctx.work_rows, ctx.work = log2_T, work_rows, work
         if work is None and any(ctx.needs_input_grad[i] for i in (4, 5, 6, 7)):
@@ -104,10 +101,7 @@ class _HashSdf(Function):
         work = (ctx.work if ctx.work is not None else work_buffer(x01.device)) if dense else None
         rows = int(ctx.work_rows) if ctx.work_rows is not None else MAX_ROWS
         with _lib.timed("k_hashsdf_bwd", (2.0 * S * (3 * HID * ENC), 4.0 * S * (2 * 8 * L * F + 3 + 4))):
-            _lib.check(_lib.lib().lab4d_hashsdf_backward(_lib.ptr(x01), _lib.ptr(table), _lib.ptr(res), S, L, ctx.log2_T, F, _lib.ptr(W1), _lib.ptr(b1),
-                                                         _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(g_sdf), _lib.ptr(g_grad01), _lib.ptr(g_table), _lib.ptr(g_W1),
-                                                         _lib.ptr(g_b1), _lib.ptr(g_w2), _lib.ptr(g_b2), _lib.ptr(work), rows, _lib.stream()),
-                       "hashsdf_backward")
+            _lib.call("hashsdf_backward", x01, table, res, S, L, ctx.log2_T, F, W1, b1, w2, b2, g_sdf, g_grad01, g_table, g_W1, g_b1, g_w2, g_b2, work, rows)
         return None, g_table, None, None, g_W1, g_b1, g_w2, g_b2, None, None
 
 

@@ -58,13 +58,11 @@ def keep_largest_component(verts, faces):
     V, F = verts.shape[0], faces.shape[0]
     if V == 0:
         return verts, faces
-    lib = _lib.lib()
-    work = torch.empty(int(lib.lab4d_mesh_component_work_ints(V, F)), dtype=torch.int32, device=verts.device)
+    work = torch.empty(int(_lib.lib().lab4d_mesh_component_work_ints(V, F)), dtype=torch.int32, device=verts.device)
     out_v, out_f = torch.empty_like(verts), torch.empty_like(faces)
     counts = torch.empty(2, dtype=torch.int32, device=verts.device)
     stats = (ctypes.c_int * 2)()
-    _lib.check(lib.lab4d_mesh_largest_component(_lib.ptr(verts), _lib.ptr(faces), V, F, _lib.ptr(work), _lib.ptr(out_v), _lib.ptr(out_f), _lib.ptr(counts),
-                                                stats, _lib.stream()), "mesh_largest_component")
+    _lib.call("mesh_largest_component", verts, faces, V, F, work, out_v, out_f, counts, stats)
     LAST["label_passes"], LAST["label_readbacks"] = int(stats[0]), int(stats[1])
     LAST["readbacks"] += int(stats[1])
     nv, nf = _read_pair(counts)
@@ -87,23 +85,21 @@ def marching_cubes(sdf, mask=None, level=0.0, origin=(0, 0, 0), step=(1, 1, 1), 
             raise RuntimeError("lab4d_amd.mesh.marching_cubes: mask must be bool / uint8 of the volume's shape")
         mask = mask.view(torch.uint8)
     LAST.update(readbacks=0, label_passes=0, label_readbacks=0)
-    lib = _lib.lib()
     Gx, Gy, Gz = (int(g) for g in sdf.shape)
-    n_work = int(lib.lab4d_mesh_work_ints(Gx, Gy, Gz))
+    n_work = int(_lib.lib().lab4d_mesh_work_ints(Gx, Gy, Gz))
     if n_work < 0:
         raise RuntimeError("lab4d_amd.mesh.marching_cubes: unsupported grid %d x %d x %d (every dimension >= 1, fewer than 2^31 / 3 points)" % (Gx, Gy, Gz))
     dev = sdf.device
     xf = _xform(origin, step, dev)
     work = torch.empty(n_work, dtype=torch.int32, device=dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
-    _lib.check(lib.lab4d_mesh_count(_lib.ptr(sdf), _lib.ptr(mask), Gx, Gy, Gz, float(level), _lib.ptr(work), _lib.ptr(counts), _lib.stream()), "mesh_count")
+    _lib.call("mesh_count", sdf, mask, Gx, Gy, Gz, float(level), work, counts)
     V, F = _read_pair(counts)
     verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
     faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
     if V == 0:
         return verts, faces
-    _lib.check(lib.lab4d_mesh_emit(_lib.ptr(sdf), Gx, Gy, Gz, float(level), _lib.ptr(xf), _lib.ptr(work), V, F, _lib.ptr(verts), _lib.ptr(faces), _lib.stream()),
-               "mesh_emit")
+    _lib.call("mesh_emit", sdf, Gx, Gy, Gz, float(level), xf, work, V, F, verts, faces)
     if largest_component:
         return keep_largest_component(verts, faces)
     return verts, faces

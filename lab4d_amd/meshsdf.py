@@ -71,12 +71,10 @@ def signed_distance(verts, faces, pts, n_slices=None, return_face=False, return_
     sdf = torch.empty(N, dtype=torch.float32, device=pts.device)
     face = torch.empty(N, dtype=torch.int32, device=pts.device) if return_face else None
     closest = torch.empty(N, 3, dtype=torch.float32, device=pts.device) if return_closest else None
-    lib = _lib.lib()
     for o in range(0, N, chunk):
         n = min(chunk, N - o)
-        _lib.check(lib.lab4d_mesh_sdf(_lib.ptr(verts), _lib.ptr(faces), verts.shape[0], F, _lib.ptr(flat[o:o + n]), n, n_slices,
-                                      _lib.ptr(work) if n_slices > 1 else None, _lib.ptr(sdf[o:o + n]), None if face is None else _lib.ptr(face[o:o + n]),
-                                      None if closest is None else _lib.ptr(closest[o:o + n]), _lib.stream()), "mesh_sdf")
+        _lib.call("mesh_sdf", verts, faces, verts.shape[0], F, flat[o:o + n], n, n_slices, work if n_slices > 1 else None, sdf[o:o + n],
+                  None if face is None else face[o:o + n], None if closest is None else closest[o:o + n])
     out = (sdf.reshape(lead),)
     if return_face:
         out += (face.reshape(lead),)

@@ -140,7 +140,7 @@ _DESC = {}
 def describe(net):
     if net not in _DESC:
         d = NetDesc()
-        _lib.check(_lib.lib().lab4d_mlp_describe(net, ctypes.byref(d)), "mlp_describe")
+        _lib.call("mlp_describe", net, ctypes.byref(d))
         _DESC[net] = d
     return _DESC[net]
 
@@ -341,8 +341,7 @@ def _pack_into(net, layer, prec, W, transposed, out=None):
     if out is None or ALWAYS_PACK:
         out = torch.empty(L.mout_pad * (L.ke + L.kin), dtype=store_dtype(prec), device=W.device)
     cm = col_map(net, layer, W.device)
-    _lib.check(_lib.lib().lab4d_mlp_pack(net, layer, prec, 1 if transposed else 0, _lib.ptr(Wc), Wc.shape[1], _lib.ptr(cm),
-                                         _lib.ptr(out), _lib.stream()), "mlp_pack")
+    _lib.call("mlp_pack", net, layer, prec, 1 if transposed else 0, Wc, Wc.shape[1], cm, out)
     return out
 
 
@@ -493,13 +492,10 @@ def collect_wgrads(net, prec, S, S_pad, spf, M, Ws, bs, emb, layers, eikonal=Fal
             pfd = arena[aoff + n0 + n1:aoff + n0 + n1 + n2].view(M, L.mout_pad) if need_pf else None
             with _lib.timed(wgrad_kernel_name(L, prec) + tag, wgrad_work(L, S_pad, prec)):
                 if sw is not None:
-                    _lib.check(_lib.lib().lab4d_mlp_wgrad_mapped(net, l, prec, S, S_pad, S_pad, spf, _lib.ptr(dz), _lib.ptr(emb), _lib.ptr(prev),
-                                                                 _lib.ptr(sw), sw.shape[1], _lib.ptr(col_map(net, l, dev)),
-                                                                 _lib.ptr(sb if sb is not None else dbk), _lib.ptr(pfd), M, _lib.stream()),
-                               "mlp_wgrad_mapped" + what)
+                    _lib.call("mlp_wgrad_mapped", net, l, prec, S, S_pad, S_pad, spf, dz, emb, prev, sw, sw.shape[1], col_map(net, l, dev),
+                              sb if sb is not None else dbk, pfd, M, what="mlp_wgrad_mapped" + what)
                 else:
-                    _lib.check(_lib.lib().lab4d_mlp_wgrad(net, l, prec, S, S_pad, S_pad, spf, _lib.ptr(dz), _lib.ptr(emb), _lib.ptr(prev),
-                                                          _lib.ptr(dWk), _lib.ptr(dbk), _lib.ptr(pfd), M, _lib.stream()), "mlp_wgrad" + what)
+                    _lib.call("mlp_wgrad", net, l, prec, S, S_pad, S_pad, spf, dz, emb, prev, dWk, dbk, pfd, M, what="mlp_wgrad" + what)
             if need_w and sw is None:
                 gW = _to_reference(net, l, Ws[l], dWk)
             if need_b and sb is None:
@@ -618,7 +614,7 @@ def chain_forward(net, prec, spf, x, pfs, params, want, ext=None, freq_w=None, e
     # algorithmic HBM bytes of this launch: every stored tensor written once, inputs read once
     nbytes = sum(t.numel() * t.element_size() for t in acts + masks + [emb, ext, out, x] if t is not None)
     with _lib.timed(chain_kernel_name("fwd", net, prec, dx_only) + ("" if store else " inference"), (2.0 * S * NET_MACS[net], float(nbytes))):
-        _lib.check(_lib.lib().lab4d_mlp_forward(ctypes.byref(a), _lib.stream()), "mlp_forward")
+        _lib.call("mlp_forward", ctypes.byref(a))
     if tap is not None and need_grad:  # the training-mode pass's ReLU sign words and stored embedding, for EikonalSdf (references, not copies)
         tap.update(net=net, prec=prec, S=S, S_pad=S_pad, masks=list(masks), emb=emb)
     st = ChainState(net=net, prec=prec, spf=spf, S=S, S_pad=S_pad, want=want, params=params, pf_used=pf_used, acts=acts, masks=masks, emb=emb,
@@ -676,7 +672,7 @@ def chain_backward(st, d_out, d_export=None):
     nbytes = sum(t.numel() * t.element_size() for t in list(dz) + list(st.masks) + [d_out, d_x, ext_g, st.emb if d_x is not None else None, d_export]
                  if t is not None)
     with _lib.timed(chain_kernel_name("bwd", net, prec, st.dx_only), (2.0 * S * NET_MACS[net], float(nbytes))):
-        _lib.check(_lib.lib().lab4d_mlp_backward(ctypes.byref(a), _lib.stream()), "mlp_backward")
+        _lib.call("mlp_backward", ctypes.byref(a))
     # a per-frame table is an input of its own: when nothing upstream of it wants a gradient (the eval path's normals differentiate wrt the points
     # only) and neither do the layer's parameters, the layer needs no weight-gradient launch at all
     need_pf = iter(want.pfs)
@@ -744,7 +740,7 @@ def chain_backward_fused(st, d_out):
             a.bias[l], a.db[l] = _lib.dp(f["bias"][l]), _lib.dp(dbk)
     nbytes = 4.0 * S * (3 + d.c_out + (3 if d_x is not None else 0))
     with _lib.timed("k_mlp_bwd_fused<%s>" % KERNEL_NET[net], (2.0 * S * NET_MACS[net] * 3, nbytes)):  # recompute + dgrad + wgrad
-        _lib.check(_lib.lib().lab4d_mlp_backward_fused(ctypes.byref(a), _lib.stream()), "mlp_backward_fused")
+        _lib.call("mlp_backward_fused", ctypes.byref(a))
     grads_pf, grads_params = [], []
     need_pf = iter(want.pfs)
     for l in range(NL):
@@ -847,7 +843,7 @@ def run_chain_compacted(net, prec, P, x, frame_idx, count, conds=None, ext=None,
     out = torch.empty(S, d.c_out, device=dev)
     a.out = _lib.dp(out)
     with _lib.timed(chain_kernel_name("fwd", net, prec) + " inference", (2.0 * S * NET_MACS[net], 0.0)):
-        _lib.check(_lib.lib().lab4d_mlp_forward(ctypes.byref(a), _lib.stream()), "mlp_forward(compacted)")
+        _lib.call("mlp_forward", ctypes.byref(a), what="mlp_forward(compacted)")
     return (out, exported) if exported is not None else out
 
 
@@ -911,7 +907,7 @@ class EikonalSdf(Function):
                 reused = True
         if not reused:
             with _lib.timed(chain_kernel_name("fwd", net, prec) + "@eik"):
-                _lib.check(_lib.lib().lab4d_mlp_forward(ctypes.byref(a), _lib.stream()), "mlp_forward(eikonal primal)")
+                _lib.call("mlp_forward", ctypes.byref(a), what="mlp_forward(eikonal primal)")
         bk, packed_t, dz, zero_gin = bind_backward(net, prec, S, S_pad, spf, Ws, masks)  # held until the launch has returned
         bk.emb = _lib.dp(emb)
         ones = torch.ones(S, 1, device=dev)
@@ -919,7 +915,7 @@ class EikonalSdf(Function):
         g = torch.empty(S, 3, device=dev)
         bk.d_x = _lib.dp(g)
         with _lib.timed(chain_kernel_name("bwd", net, prec) + "@eik"):
-            _lib.check(_lib.lib().lab4d_mlp_backward(ctypes.byref(bk), _lib.stream()), "mlp_backward(eikonal primal)")
+            _lib.call("mlp_backward", ctypes.byref(bk), what="mlp_backward(eikonal primal)")
         gn = g.norm(2, dim=-1, keepdim=True)
         ctx.meta = (net, prec, spf, S, S_pad)
         ctx.saved = (x, fw, g, gn, dz, masks, packed, tact)
@@ -938,8 +934,7 @@ class EikonalSdf(Function):
         # dL/dg, then u = J_e(x) dL/dg in embedding-slot order [ (f, a, {sin,cos}) pairs | x | pad ]
         # zero sdf gradient (every unit of a layer dead): torch's norm backward takes the zero subgradient there, not 0/0
         u = torch.empty(S, d.ke, device=dev)
-        _lib.check(_lib.lib().lab4d_eikonal_tangent_input(_lib.ptr(x), _lib.ptr(g), _lib.ptr(ge.contiguous().float()), _lib.ptr(fw), S, L0, d.ke, _lib.ptr(u),
-                                                          _lib.stream()), "eikonal_tangent_input")
+        _lib.call("eikonal_tangent_input", x, g, ge.contiguous().float(), fw, S, L0, d.ke, u)
         a = FwdArgs()
         a.net, a.precision, a.S, a.S_pad, a.ld, a.spf = net, prec, S, S_pad, S_pad, spf
         a.x = _lib.dp(u)
@@ -952,7 +947,7 @@ class EikonalSdf(Function):
         temb = torch.empty(buf_numel(d.ke, S_pad), dtype=sdt, device=dev)
         a.emb = _lib.dp(temb)
         with _lib.timed(("k_mlp_fwd_ws_tangent<%s>@eik" if (ws_active(net, prec) and net == NET_FG_BASE) else "k_mlp_fwd_tangent<%s>@eik") % KERNEL_NET[net]):
-            _lib.check(_lib.lib().lab4d_mlp_forward_tangent(ctypes.byref(a), _lib.stream()), "mlp_forward_tangent")
+            _lib.call("mlp_forward_tangent", ctypes.byref(a))
         need_w = ctx.needs_input_grad[-2 * NL:][0::2]  # the parameters are the trailing inputs; biases get no gradient from this term
         layers = [(dz[l], tact[l - 1] if d.layers[l].kin else None, need_w[l], False, False) for l in range(NL)]
         grads = collect_wgrads(net, prec, S, S_pad, spf, 0, Ws, bs, temb, layers, eikonal=True)

@@ -15,7 +15,7 @@ def compose_order(depth_a, depth_b):
     R = da.shape[0] * da.shape[1]
     order = torch.empty(R, Da + Db, dtype=torch.int32, device=da.device)
     pos = torch.empty_like(order)
-    _lib.check(_lib.lib().lab4d_compose_order(_lib.ptr(da), Da, _lib.ptr(db), Db, R, _lib.ptr(order), _lib.ptr(pos), _lib.stream()), "compose_order")
+    _lib.call("compose_order", da, Da, db, Db, R, order, pos)
     return order, pos
 
 
@@ -30,8 +30,7 @@ class _ComposeGather(Function):
         a_c = a.contiguous().float() if a is not None else None
         b_c = b.contiguous().float() if b is not None else None
         out = torch.empty(M, N, Da + Db, C, device=ref.device)
-        _lib.check(_lib.lib().lab4d_compose_gather(_lib.ptr(a_c), Da, _lib.ptr(b_c), Db, _lib.ptr(order), Da + Db, R, Da + Db, C, _lib.ptr(out),
-                                                   _lib.stream()), "compose_gather")
+        _lib.call("compose_gather", a_c, Da, b_c, Db, order, Da + Db, R, Da + Db, C, out)
         ctx.save_for_backward(pos)
         ctx.meta = (M, N, Da, Db, C, a is not None, b is not None)
         return out
@@ -46,13 +45,11 @@ class _ComposeGather(Function):
         ga = gb = None
         if has_a and ctx.needs_input_grad[0]:
             ga = torch.empty(M, N, Da, C, device=g.device)
-            _lib.check(_lib.lib().lab4d_compose_gather(_lib.ptr(g), Dt, None, 0, _lib.ptr(pos), Dt, R, Da, C, _lib.ptr(ga), _lib.stream()),
-                       "compose_gather(adjoint a)")
+            _lib.call("compose_gather", g, Dt, None, 0, pos, Dt, R, Da, C, ga, what="compose_gather(adjoint a)")
         if has_b and ctx.needs_input_grad[1]:
             gb = torch.empty(M, N, Db, C, device=g.device)
             pos_b = pos[:, Da:]  # row stride stays Dt: pass the offset view's pointer
-            _lib.check(_lib.lib().lab4d_compose_gather(_lib.ptr(g), Dt, None, 0, _lib.ptr_at(pos_b), Dt, R, Db, C, _lib.ptr(gb), _lib.stream()),
-                       "compose_gather(adjoint b)")
+            _lib.call("compose_gather", g, Dt, None, 0, _lib.ptr_at(pos_b), Dt, R, Db, C, gb, what="compose_gather(adjoint b)")
         return ga, gb, None, None, None, None
 
 

@@ -44,8 +44,7 @@ class OccupancyGrid:
         if density.dtype != torch.float32 or density.numel() != self.G ** 3 or tuple(density.shape) not in ((self.G,) * 3, (self.G ** 3,)):
             raise RuntimeError("lab4d_amd.occgrid.update needs a (G, G, G) or (G^3,) float32 density with G = %d, got %s %s"
                                % (self.G, density.dtype, tuple(density.shape)))
-        _lib.check(_lib.lib().lab4d_occgrid_update(_lib.ptr(density), _lib.ptr(self.ema), _lib.ptr(self.bits), _lib.ptr(self.n_occupied), self.G,
-                                                   self.decay, self.thresh, _lib.stream()), "occgrid_update")
+        _lib.call("occgrid_update", density, self.ema, self.bits, self.n_occupied, self.G, self.decay, self.thresh)
         return self
 
     @torch.no_grad()
@@ -55,8 +54,7 @@ class OccupancyGrid:
         xyz = xyz.detach()
         S = xyz.numel() // 3
         out = torch.empty(S, dtype=torch.uint8, device=xyz.device)
-        _lib.check(_lib.lib().lab4d_occgrid_mask(_lib.ptr(xyz), _lib.ptr(self.aabb), _lib.ptr(self.bits), self.G, S, _lib.ptr(out), _lib.stream()),
-                   "occgrid_mask")
+        _lib.call("occgrid_mask", xyz, self.aabb, self.bits, self.G, S, out)
         return out
 
     @torch.no_grad()
@@ -72,8 +70,7 @@ class OccupancyGrid:
                                % (tuple(origin.shape), tuple(dir.shape), tuple(t_range.shape)))
         t_span = torch.empty(R, 2, dtype=torch.float32, device=origin.device)
         hit = torch.empty(R, dtype=torch.uint8, device=origin.device)
-        _lib.check(_lib.lib().lab4d_occgrid_ray_span(_lib.ptr(origin.detach()), _lib.ptr(dir.detach()), _lib.ptr(t_range.detach()), _lib.ptr(self.aabb),
-                                                     _lib.ptr(self.bits), self.G, R, _lib.ptr(t_span), _lib.ptr(hit), _lib.stream()), "occgrid_ray_span")
+        _lib.call("occgrid_ray_span", origin.detach(), dir.detach(), t_range.detach(), self.aabb, self.bits, self.G, R, t_span, hit)
         return t_span, hit.view(torch.bool)
 
     @torch.no_grad()
@@ -81,7 +78,7 @@ class OccupancyGrid:
         """Depths for sample_cam_rays(depth=...): origin, dir (...,3) in the field's frame, near_far (...,2) or one pair per leading index
         ((M,2) for (M,N,3) rays) -> (depth (..., n_depth, 1), hit (...) bool).  A hit ray's depths are evenly spaced over its span, the first
         equal to t_first and the last to t_last; a ray without a hit keeps its original range (the caller masks it)."""
-        _lib.require_device(*(t for t in (origin, dir, near_far) if not t.is_cuda))  # (raises: there is no CPU path)
+        _lib.require_device(origin, dir, near_far)
         origin = origin.contiguous()
         lead = origin.shape[:-1]
         nf = near_far

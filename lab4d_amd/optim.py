@@ -66,19 +66,15 @@ class FlatAdamW:
 
     def grad_norm_clip(self, max_norm):
         """Global gradient norm and clip_grad_norm_'s coefficient, both left on the device (no host sync); returns the norm."""
-        _lib.require_device(self.flat_grad)
-        _lib.check(_lib.lib().lab4d_grad_norm_clip(_lib.ptr(self.flat_grad), self.n, float(max_norm), _lib.ptr(self.work), _lib.ptr(self.norm),
-                                                   _lib.ptr(self.coef), _lib.stream()), "grad_norm_clip")
+        _lib.call("grad_norm_clip", self.flat_grad, self.n, float(max_norm), self.work, self.norm, self.coef)
         return self.norm
 
     def check_grad(self, max_norm, skip_above=None):
         """Trainer.check_grad (engine/trainer.py:581-604) on the device: the global gradient norm, clip_grad_norm_'s coefficient and the
         discard decision (pre-clip norm > skip_above, default max_norm like the reference, or not finite) -- `norm`, `coef`, `skipped` stay on
         the device, the NEXT step() applies them; no host synchronisation.  Returns the norm tensor."""
-        _lib.require_device(self.flat_grad)
         thresh = float(max_norm if skip_above is None else skip_above)
-        _lib.check(_lib.lib().lab4d_check_grad(_lib.ptr(self.flat_grad), self.n, float(max_norm), thresh, _lib.ptr(self.work), _lib.ptr(self.norm),
-                                               _lib.ptr(self.coef), _lib.ptr(self.skipped), _lib.ptr(self.dev_step), _lib.stream()), "check_grad")
+        _lib.call("check_grad", self.flat_grad, self.n, float(max_norm), thresh, self.work, self.norm, self.coef, self.skipped, self.dev_step)
         self._checked = True
         self._guarded_used = True
         return self.norm
@@ -99,18 +95,14 @@ class FlatAdamW:
             self.check_grad(max_norm, skip_above)
         if getattr(self, "_checked", False):
             self._checked = False
-            _lib.check(_lib.lib().lab4d_adamw_step_guarded(_lib.ptr(self.flat), _lib.ptr(self.flat_grad), _lib.ptr(self.m), _lib.ptr(self.v), self.n,
-                                                           _lib.ptr(self.seg_end), _lib.ptr(self.seg_lr), len(self.params), self.betas[0],
-                                                           self.betas[1], self.eps, self.weight_decay, _lib.ptr(self.coef), _lib.ptr(self.skipped),
-                                                           _lib.ptr(self.dev_step), _lib.stream()), "adamw_step_guarded")
+            _lib.call("adamw_step_guarded", self.flat, self.flat_grad, self.m, self.v, self.n, self.seg_end, self.seg_lr, len(self.params), self.betas[0],
+                      self.betas[1], self.eps, self.weight_decay, self.coef, self.skipped, self.dev_step)
             torch.autograd.graph.increment_version(self.params)
             return
         if max_norm is not None:
             self.grad_norm_clip(max_norm)
-        _lib.check(_lib.lib().lab4d_adamw_step(_lib.ptr(self.flat), _lib.ptr(self.flat_grad), _lib.ptr(self.m), _lib.ptr(self.v), self.n,
-                                               _lib.ptr(self.seg_end), _lib.ptr(self.seg_lr), len(self.params), self.betas[0], self.betas[1], self.eps,
-                                               self.weight_decay, self._taken(), _lib.ptr(self.coef) if max_norm is not None else None, _lib.stream()),
-                   "adamw_step")
+        _lib.call("adamw_step", self.flat, self.flat_grad, self.m, self.v, self.n, self.seg_end, self.seg_lr, len(self.params), self.betas[0], self.betas[1],
+                  self.eps, self.weight_decay, self._taken(), self.coef if max_norm is not None else None)
         # the kernel wrote through raw pointers: tell autograd (and the packed-weight caches keyed on it) that the data changed
         torch.autograd.graph.increment_version(self.params)
 

@@ -54,16 +54,15 @@ def march(grid, origin, dir, t_range, dt, cap, k_max=1024):
     dev = origin.device
     origin, dir, t_range = origin.detach(), dir.detach(), t_range.detach()
     count = torch.empty(R, dtype=torch.int32, device=dev)
-    head = (_lib.ptr(origin), _lib.ptr(dir), _lib.ptr(t_range), _lib.ptr(grid.aabb), _lib.ptr(grid.bits), grid.G, R, dt, k_max)
-    _lib.check(_lib.lib().lab4d_packed_march_count(*head, _lib.ptr(count), _lib.stream()), "packed_march_count")
+    head = [origin, dir, t_range, grid.aabb, grid.bits, grid.G, R, dt, k_max]
+    _lib.call("packed_march_count", *head, count)
     start = torch.cumsum(count, 0, dtype=torch.int32) - count  # (the exclusive scan: R * k_max < 2^31, the sums fit)
     out = {"t": torch.empty(cap, device=dev), "deltas": torch.empty(cap, device=dev), "xyz": torch.empty(cap, 3, device=dev),
            "dirs": torch.empty(cap, 3, device=dev), "ray_idx": torch.empty(cap, dtype=torch.int32, device=dev),
            "ray_count": torch.empty(R, dtype=torch.int32, device=dev), "total": torch.empty(1, dtype=torch.int32, device=dev)}
     overflow = torch.empty(1, dtype=torch.uint8, device=dev)
-    _lib.check(_lib.lib().lab4d_packed_march_write(*head, _lib.ptr(start), cap, _lib.ptr(out["t"]), _lib.ptr(out["deltas"]), _lib.ptr(out["xyz"]),
-                                                   _lib.ptr(out["dirs"]), _lib.ptr(out["ray_idx"]), _lib.ptr(out["ray_count"]), _lib.ptr(out["total"]),
-                                                   _lib.ptr(overflow), _lib.stream()), "packed_march_write")
+    _lib.call("packed_march_write", *head, start, cap, out["t"], out["deltas"], out["xyz"], out["dirs"], out["ray_idx"], out["ray_count"], out["total"],
+              overflow)
     return PackedRays(ray_start=start, overflow=overflow.view(torch.bool), R=R, cap=cap, **out)
 
 
@@ -86,8 +85,7 @@ class _PackedComposite(Function):
         fl, sumC = _field_list(fields, modes)
         mask = torch.empty(R, 1, device=density.device)
         out = torch.empty(R, max(sumC, 1), device=density.device)
-        _lib.check(_lib.lib().lab4d_packed_composite_forward(_lib.ptr(density), _lib.ptr(deltas), fl, _lib.ptr(ray_start), _lib.ptr(ray_count), R, P, None, None,
-                                                             _lib.ptr(mask), _lib.ptr(out), _lib.stream()), "packed_composite_forward")
+        _lib.call("packed_composite_forward", density, deltas, fl, ray_start, ray_count, R, P, None, None, mask, out)
         ctx.save_for_backward(density, deltas, ray_start, ray_count, *fields)
         ctx.modes = tuple(modes)
         return mask, out
@@ -109,9 +107,7 @@ class _PackedComposite(Function):
         g_deltas = torch.zeros_like(deltas) if ctx.needs_input_grad[1] else None
         g_mask = g_mask.contiguous() if g_mask is not None else None
         g_out = g_out.contiguous() if g_out is not None else None
-        _lib.check(_lib.lib().lab4d_packed_composite_backward(_lib.ptr(density), _lib.ptr(deltas), fl, _lib.ptr(ray_start), _lib.ptr(ray_count), R, P,
-                                                              _lib.ptr(g_mask), _lib.ptr(g_out), _lib.ptr(g_density), _lib.ptr(g_deltas), gf, _lib.stream()),
-                   "packed_composite_backward")
+        _lib.call("packed_composite_backward", density, deltas, fl, ray_start, ray_count, R, P, g_mask, g_out, g_density, g_deltas, gf)
         return (g_density, g_deltas, None, None, None, *gfields)
 
 

@@ -56,8 +56,7 @@ class _Fk(Function):
         _lib.require_device(so3, local, shift_c)
         R, B = so3.shape[:2]
         qr, qd = torch.empty(R, B, 4, device=so3.device), torch.empty(R, B, 4, device=so3.device)
-        _lib.check(_lib.lib().lab4d_fk_forward(_lib.ptr(so3), _lib.ptr(local), _lib.ptr(shift_c), _lib.ptr(order), _lib.ptr(parent), R, B,
-                                               int(bones), _lib.ptr(qr), _lib.ptr(qd), _lib.stream()), "fk_forward")
+        _lib.call("fk_forward", so3, local, shift_c, order, parent, R, B, int(bones), qr, qd)
         ctx.save_for_backward(so3, local, shift_c if shift_c is not None else so3.new_empty(0), order, parent)
         ctx.meta = (int(bones), shift is not None)
         return qr, qd
@@ -71,9 +70,7 @@ class _Fk(Function):
         g_qr, g_qd = g_qr.contiguous().float(), g_qd.contiguous().float()
         g_so3, g_local = torch.empty_like(so3), torch.empty_like(local)
         g_shift = torch.empty(R, 3, device=so3.device) if has_shift else None
-        _lib.check(_lib.lib().lab4d_fk_backward(_lib.ptr(so3), _lib.ptr(local), _lib.ptr(shift) if has_shift else None, _lib.ptr(order),
-                                                _lib.ptr(parent), _lib.ptr(g_qr), _lib.ptr(g_qd), R, B, bones, _lib.ptr(g_so3), _lib.ptr(g_local),
-                                                _lib.ptr(g_shift), _lib.stream()), "fk_backward")
+        _lib.call("fk_backward", so3, local, shift if has_shift else None, order, parent, g_qr, g_qd, R, B, bones, g_so3, g_local, g_shift)
         return g_so3, g_local, (g_shift.sum(0) if has_shift else None), None, None, None
 
 
@@ -87,8 +84,7 @@ class _CameraEpilogue(Function):
         _lib.require_device(raw, basec)
         M, V = raw.shape[0], basec.shape[0]
         out = torch.empty(M, 4, device=raw.device)
-        _lib.check(_lib.lib().lab4d_camera_epilogue_forward(_lib.ptr(raw), _lib.ptr(basec), _lib.ptr(frame_id), _lib.ptr(vid), M, V, _lib.ptr(out), _lib.stream()),
-                   "camera_epilogue_forward")
+        _lib.call("camera_epilogue_forward", raw, basec, frame_id, vid, M, V, out)
         ctx.save_for_backward(raw, basec, frame_id, vid)
         ctx.base_ref = base
         return out
@@ -103,8 +99,7 @@ class _CameraEpilogue(Function):
         g_raw, scratch = torch.empty_like(raw), torch.empty_like(raw)
         sink = mlp._grad_sink(ctx.base_ref) if ctx.needs_input_grad[1] else None
         g_base = sink if sink is not None else (torch.empty_like(base) if ctx.needs_input_grad[1] else None)
-        _lib.check(_lib.lib().lab4d_camera_epilogue_backward(_lib.ptr(raw), _lib.ptr(base), _lib.ptr(frame_id), _lib.ptr(vid), _lib.ptr(g), M, V, _lib.ptr(g_raw),
-                                                             _lib.ptr(scratch), _lib.ptr(g_base), int(sink is not None), _lib.stream()), "camera_epilogue_backward")
+        _lib.call("camera_epilogue_backward", raw, base, frame_id, vid, g, M, V, g_raw, scratch, g_base, int(sink is not None))
         return g_raw, (None if sink is not None else g_base), None, None
 
 
@@ -117,8 +112,7 @@ class _IntrinsicsEpilogue(Function):
         _lib.require_device(raw, lf, pp)
         M, V = raw.shape[0], lf.shape[0]
         out = torch.empty(M, 4, device=raw.device)
-        _lib.check(_lib.lib().lab4d_intrinsics_epilogue_forward(_lib.ptr(raw), _lib.ptr(lf), _lib.ptr(pp), _lib.ptr(frame_id), _lib.ptr(vid), M, V, _lib.ptr(out),
-                                                                _lib.stream()), "intrinsics_epilogue_forward")
+        _lib.call("intrinsics_epilogue_forward", raw, lf, pp, frame_id, vid, M, V, out)
         ctx.save_for_backward(raw, lf, frame_id, vid)
         return out
 
@@ -129,8 +123,7 @@ class _IntrinsicsEpilogue(Function):
         M, V = raw.shape[0], lf.shape[0]
         g = g.contiguous().float()
         g_raw, scratch, g_video = torch.empty_like(raw), torch.empty(M, 4, device=raw.device), torch.empty(V, 4, device=raw.device)
-        _lib.check(_lib.lib().lab4d_intrinsics_epilogue_backward(_lib.ptr(raw), _lib.ptr(lf), _lib.ptr(frame_id), _lib.ptr(vid), _lib.ptr(g), M, V, _lib.ptr(g_raw),
-                                                                 _lib.ptr(scratch), _lib.ptr(g_video), _lib.stream()), "intrinsics_epilogue_backward")
+        _lib.call("intrinsics_epilogue_backward", raw, lf, frame_id, vid, g, M, V, g_raw, scratch, g_video)
         return g_raw, g_video[:, :2], g_video[:, 2:], None, None
 
 
@@ -165,9 +158,7 @@ class _SkelBones(Function):
         _lib.require_device(so3, loglen, logscale, rest_local, shift)
         R, B = so3.shape[:2]
         qr, qd = torch.empty(R, B, 4, device=so3.device), torch.empty(R, B, 4, device=so3.device)
-        _lib.check(_lib.lib().lab4d_skel_bones_forward(_lib.ptr(so3), _lib.ptr(loglen), _lib.ptr(logscale), _lib.ptr(rest_local), _lib.ptr(shift),
-                                                       _lib.ptr(order), _lib.ptr(parent), _lib.ptr(symm), R, B, _lib.ptr(qr), _lib.ptr(qd),
-                                                       _lib.stream()), "skel_bones_forward")
+        _lib.call("skel_bones_forward", so3, loglen, logscale, rest_local, shift, order, parent, symm, R, B, qr, qd)
         ctx.save_for_backward(so3, loglen, logscale, rest_local, shift, order, parent, symm)
         return qr, qd
 
@@ -179,10 +170,7 @@ class _SkelBones(Function):
         g_qr, g_qd = g_qr.contiguous().float(), g_qd.contiguous().float()
         g_so3, g_ll = torch.empty_like(so3), torch.empty_like(loglen)
         g_ls, g_sh = torch.empty(R, device=so3.device), torch.empty(R, 3, device=so3.device)
-        _lib.check(_lib.lib().lab4d_skel_bones_backward(_lib.ptr(so3), _lib.ptr(loglen), _lib.ptr(logscale), _lib.ptr(rest_local), _lib.ptr(shift),
-                                                        _lib.ptr(order), _lib.ptr(parent), _lib.ptr(symm), _lib.ptr(g_qr), _lib.ptr(g_qd), R, B,
-                                                        _lib.ptr(g_so3), _lib.ptr(g_ll), _lib.ptr(g_ls), _lib.ptr(g_sh), _lib.stream()),
-                   "skel_bones_backward")
+        _lib.call("skel_bones_backward", so3, loglen, logscale, rest_local, shift, order, parent, symm, g_qr, g_qd, R, B, g_so3, g_ll, g_ls, g_sh)
         return g_so3, g_ll, g_ls.sum().reshape(logscale.shape), None, g_sh.sum(0), None, None, None
 
 

@@ -31,8 +31,7 @@ class _QuaternionMulBackward(Function):
         code = _chk(grad, a, b)
         B, D1, D2 = a.shape[0], a.shape[1], b.shape[1]
         ga, gb = torch.empty_like(a), torch.empty_like(b)
-        _lib.check(_lib.lib().lab4d_quaternion_mul_backward(_lib.ptr(grad), B, D1, D2, _lib.ptr(a), _lib.ptr(b), _lib.ptr(ga),
-                                                            _lib.ptr(gb), code, _lib.stream()), "quaternion_mul_backward")
+        _lib.call("quaternion_mul_backward", grad, B, D1, D2, a, b, ga, gb, code)
         ctx.save_for_backward(grad, a, b)
         return ga, gb
 
@@ -44,9 +43,7 @@ class _QuaternionMulBackward(Function):
         code = _chk(grad, a, b, go1, go2)
         B, D1, D2 = a.shape[0], a.shape[1], b.shape[1]
         gg, gga, ggb = torch.empty_like(grad), torch.empty_like(a), torch.empty_like(b)
-        _lib.check(_lib.lib().lab4d_quaternion_mul_backward_backward(
-            _lib.ptr(go1), _lib.ptr(go2), B, D1, D2, _lib.ptr(grad), _lib.ptr(a), _lib.ptr(b), _lib.ptr(gg), _lib.ptr(gga),
-            _lib.ptr(ggb), code, _lib.stream()), "quaternion_mul_backward_backward")
+        _lib.call("quaternion_mul_backward_backward", go1, go2, B, D1, D2, grad, a, b, gg, gga, ggb, code)
         return gg, gga, ggb
 
 
@@ -58,8 +55,7 @@ class _QuaternionMul(Function):
         if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0] or a.shape[1] not in (3, 4) or b.shape[1] not in (3, 4):
             raise RuntimeError("quaternion_mul expects (B,3|4) x (B,3|4), got %s x %s" % (tuple(a.shape), tuple(b.shape)))
         out = torch.empty(a.shape[0], 4, dtype=a.dtype, device=a.device)
-        _lib.check(_lib.lib().lab4d_quaternion_mul_forward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(out), a.shape[0], a.shape[1],
-                                                           b.shape[1], code, _lib.stream()), "quaternion_mul_forward")
+        _lib.call("quaternion_mul_forward", a, b, out, a.shape[0], a.shape[1], b.shape[1], code)
         ctx.save_for_backward(a, b)
         return out
 
@@ -75,8 +71,7 @@ class _QuaternionConjugate(Function):
         q = q.contiguous()
         code = _chk(q)
         out = torch.empty_like(q)
-        _lib.check(_lib.lib().lab4d_quaternion_conjugate(_lib.ptr(q), q.numel() // 4, _lib.ptr(out), code, _lib.stream()),
-                   "quaternion_conjugate")
+        _lib.call("quaternion_conjugate", q, q.numel() // 4, out, code)
         return out
 
     @staticmethod
@@ -92,7 +87,7 @@ def mat3x3_det(m):
     x = m.contiguous().view(-1, 9)
     code = _chk(x)
     out = torch.empty(x.shape[0], dtype=x.dtype, device=x.device)
-    _lib.check(_lib.lib().lab4d_mat3x3_det_forward(_lib.ptr(x), _lib.ptr(out), x.shape[0], code, _lib.stream()), "mat3x3_det")
+    _lib.call("mat3x3_det_forward", x, out, x.shape[0], code)
     return out.view(m.shape[:-2])
 
 
@@ -100,8 +95,7 @@ def mat3x3_scale_adjoint(m, scales):
     x, s = m.contiguous().view(-1, 9), scales.contiguous().view(-1)
     code = _chk(x, s)
     out = torch.empty_like(x)
-    _lib.check(_lib.lib().lab4d_mat3x3_scale_adjoint_forward(_lib.ptr(x), _lib.ptr(s), _lib.ptr(out), x.shape[0], code,
-                                                             _lib.stream()), "mat3x3_scale_adjoint")
+    _lib.call("mat3x3_scale_adjoint_forward", x, s, out, x.shape[0], code)
     return out.view(m.shape)
 
 
@@ -110,8 +104,7 @@ class _Mat3x3Inv(Function):
     def forward(ctx, x):
         code = _chk(x)
         out, scales = torch.empty_like(x), torch.empty(x.shape[0], dtype=x.dtype, device=x.device)
-        _lib.check(_lib.lib().lab4d_mat3x3_inv_forward(_lib.ptr(x), _lib.ptr(out), _lib.ptr(scales), x.shape[0], code,
-                                                       _lib.stream()), "mat3x3_inv_forward")
+        _lib.call("mat3x3_inv_forward", x, out, scales, x.shape[0], code)
         ctx.save_for_backward(out)
         return out
 
@@ -122,8 +115,7 @@ class _Mat3x3Inv(Function):
         grad = grad.contiguous()
         code = _chk(inv, grad)
         gin = torch.empty_like(inv)
-        _lib.check(_lib.lib().lab4d_mat3x3_inv_backward(_lib.ptr(grad), _lib.ptr(inv), _lib.ptr(gin), inv.shape[0], code,
-                                                        _lib.stream()), "mat3x3_inv_backward")
+        _lib.call("mat3x3_inv_backward", grad, inv, gin, inv.shape[0], code)
         return gin
 
 

@@ -42,10 +42,7 @@ class _RaySamples(Function):
         depth = torch.empty(M, N, D, 1, device=dev)
         xyz_f = torch.empty(M, N, D, 3, device=dev) if cq is not None else None
         dir_f = torch.empty(M, N, D, 3, device=dev) if cq is not None else None
-        _lib.check(_lib.lib().lab4d_ray_samples_forward(
-            _lib.ptr(hxy), _lib.ptr(Kinv), _lib.ptr(near_far), _lib.ptr(depth_in), _lib.ptr(cq), _lib.ptr(ct), M, N, D,
-            _lib.ptr(xyz_cam), _lib.ptr(dir_cam), _lib.ptr(deltas), _lib.ptr(depth), _lib.ptr(xyz_f), _lib.ptr(dir_f),
-            _lib.stream()), "ray_samples_forward")
+        _lib.call("ray_samples_forward", hxy, Kinv, near_far, depth_in, cq, ct, M, N, D, xyz_cam, dir_cam, deltas, depth, xyz_f, dir_f)
         ctx.save_for_backward(hxy, Kinv, near_far, depth_in, cq, ct)
         ctx.dims = (M, N, D)
         ctx.mark_non_differentiable(depth)
@@ -67,10 +64,7 @@ class _RaySamples(Function):
         gK = torch.zeros(M, 3, 3, device=dev)
         gq = torch.zeros(M, 4, device=dev) if cq is not None else None
         gt = torch.zeros(M, 3, device=dev) if cq is not None else None
-        _lib.check(_lib.lib().lab4d_ray_samples_backward(
-            _lib.ptr(hxy), _lib.ptr(Kinv), _lib.ptr(near_far), _lib.ptr(depth_in), _lib.ptr(cq), _lib.ptr(ct), M, N, D,
-            _lib.ptr(g_xyz), _lib.ptr(g_dir), _lib.ptr(g_deltas), _lib.ptr(g_xyzf), _lib.ptr(g_dirf), _lib.ptr(gK),
-            _lib.ptr(gq), _lib.ptr(gt), _lib.stream()), "ray_samples_backward")
+        _lib.call("ray_samples_backward", hxy, Kinv, near_far, depth_in, cq, ct, M, N, D, g_xyz, g_dir, g_deltas, g_xyzf, g_dirf, gK, gq, gt)
         return None, gK, None, None, gq, gt, None
 
 
@@ -129,10 +123,7 @@ class _Composite(Function):
         chans = sum(f.shape[-1] for f in fields)
         ctx.chans = chans + extra
         with _lib.timed("k_composite_fwd", (0.0, 4.0 * R * D * (2 + chans + extra + 2))):
-            _lib.check(_lib.lib().lab4d_composite_forward(
-                _lib.ptr(density), _lib.ptr(deltas), fl, _lib.ptr(flow), _lib.ptr(vis), _lib.ptr(gdens), R, D, _lib.ptr(weights),
-                _lib.ptr(transmit), _lib.ptr(mask), _lib.ptr(out), _lib.ptr(flow_out), _lib.ptr(vis_num), _lib.ptr(t_sum),
-                _lib.ptr(gmask), _lib.stream()), "composite_forward")
+            _lib.call("composite_forward", density, deltas, fl, flow, vis, gdens, R, D, weights, transmit, mask, out, flow_out, vis_num, t_sum, gmask)
         ctx.save_for_backward(density, deltas, flow, vis, gdens, *fields)
         ctx.modes = tuple(modes)
         ctx.dims = (M, N, D, sumC)
@@ -170,10 +161,8 @@ class _Composite(Function):
         g_vis = torch.empty_like(vis) if (vis is not None and ctx.needs_input_grad[3]) else None
         g_gd = torch.empty_like(gdens) if (gdens is not None and ctx.needs_input_grad[4]) else None
         with _lib.timed("k_composite_bwd", (0.0, 4.0 * R * D * 2 * (2 + ctx.chans))):  # every per-sample field read once, its gradient written once
-            _lib.check(_lib.lib().lab4d_composite_backward(
-                _lib.ptr(density), _lib.ptr(deltas), fl, _lib.ptr(flow), _lib.ptr(vis), _lib.ptr(gdens), R, D, _lib.ptr(g_mask),
-                _lib.ptr(g_out), _lib.ptr(g_flow_out), _lib.ptr(g_vis_num), _lib.ptr(g_gmask), _lib.ptr(g_density),
-                _lib.ptr(g_deltas), gf, _lib.ptr(g_flow), _lib.ptr(g_vis), _lib.ptr(g_gd), _lib.stream()), "composite_backward")
+            _lib.call("composite_backward", density, deltas, fl, flow, vis, gdens, R, D, g_mask, g_out, g_flow_out, g_vis_num, g_gmask, g_density, g_deltas, gf,
+                      g_flow, g_vis, g_gd)
         return (g_density, g_deltas, g_flow, g_vis, g_gd, None, *gfields)
 
 
@@ -292,14 +281,12 @@ def sample_pdf(bins, weights, N_importance, det=False, eps=1e-5, return_inds=Fal
     samples = torch.empty(R, N_importance, device=bins.device)
     inds = torch.empty(R, N_importance, dtype=torch.int64, device=bins.device)
     if det:
-        _lib.check(_lib.lib().lab4d_sample_pdf(_lib.ptr(bins), _lib.ptr(weights), R, n_w, N_importance, float(eps), _lib.ptr(samples),
-                                               _lib.ptr(inds), _lib.stream()), "sample_pdf")
+        _lib.call("sample_pdf", bins, weights, R, n_w, N_importance, float(eps), samples, inds)
     else:
         u = torch.rand(R, N_importance, device=bins.device)
         us, order = torch.sort(u, -1)
         us = us.contiguous()
-        _lib.check(_lib.lib().lab4d_sample_pdf_u(_lib.ptr(bins), _lib.ptr(weights), _lib.ptr(us), R, n_w, N_importance, float(eps),
-                                                 _lib.ptr(samples), _lib.ptr(inds), _lib.stream()), "sample_pdf_u")
+        _lib.call("sample_pdf_u", bins, weights, us, R, n_w, N_importance, float(eps), samples, inds)
         samples = torch.empty_like(samples).scatter_(1, order, samples)
         inds = torch.empty_like(inds).scatter_(1, order, inds)
     return (samples, inds) if return_inds else samples
@@ -311,8 +298,7 @@ def sort_depth(a, b):
     _f32(a, b)
     R = a.shape[0]
     out = torch.empty(R, a.shape[1] + b.shape[1], device=a.device)
-    _lib.check(_lib.lib().lab4d_sort_depth(_lib.ptr(a), a.shape[1], _lib.ptr(b), b.shape[1], R, _lib.ptr(out), _lib.stream()),
-               "sort_depth")
+    _lib.call("sort_depth", a, a.shape[1], b, b.shape[1], R, out)
     return out
 
 
@@ -330,8 +316,7 @@ def valid_mask(xyz, xyz_t, aabb, t_aabb=None):
     t_aabb = None if t_aabb is None else t_aabb.contiguous().float()
     _lib.require_device(x, xt, aabb, t_aabb)
     mask = torch.empty(x.shape[0], dtype=torch.uint8, device=x.device)
-    _lib.check(_lib.lib().lab4d_valid_mask(_lib.ptr(x), _lib.ptr(xt), _lib.ptr(aabb), _lib.ptr(t_aabb), x.shape[0], _lib.ptr(mask), _lib.stream()),
-               "valid_mask")
+    _lib.call("valid_mask", x, xt, aabb, t_aabb, x.shape[0], mask)
     return mask
 
 
@@ -345,7 +330,7 @@ def compact(mask):
     idx = torch.empty(S, dtype=torch.int32, device=mask.device)
     count = torch.empty(1, dtype=torch.int32, device=mask.device)
     work = torch.empty(int(_lib.lib().lab4d_compact_work_ints(S)), dtype=torch.int32, device=mask.device)
-    _lib.check(_lib.lib().lab4d_compact(_lib.ptr(mask), S, _lib.ptr(idx), _lib.ptr(count), _lib.ptr(work), _lib.stream()), "compact")
+    _lib.call("compact", mask, S, idx, count, work)
     return idx, count
 
 
@@ -354,8 +339,7 @@ def gather_rows(src, idx, count):
     """(S,C) -> (S,C): row j = src[idx[j]] for j < count, zeros after."""
     src = src.contiguous().float()
     out = torch.empty_like(src)
-    _lib.check(_lib.lib().lab4d_gather_rows(_lib.ptr(src), _lib.ptr(idx), _lib.ptr(count), src.shape[0], src.shape[1], _lib.ptr(out), _lib.stream()),
-               "gather_rows")
+    _lib.call("gather_rows", src, idx, count, src.shape[0], src.shape[1], out)
     return out
 
 
@@ -367,7 +351,7 @@ class _GatherRowsAD(torch.autograd.Function):
         src = src.contiguous().float()
         _lib.require_device(src, idx, count)
         out = torch.empty(int(cap), src.shape[1], device=src.device)
-        _lib.check(_lib.lib().lab4d_gather_rows(_lib.ptr(src), _lib.ptr(idx), _lib.ptr(count), int(cap), src.shape[1], _lib.ptr(out), _lib.stream()), "gather_rows")
+        _lib.call("gather_rows", src, idx, count, int(cap), src.shape[1], out)
         ctx.save_for_backward(idx, count)
         ctx.n_rows = src.shape[0]
         return out
@@ -377,7 +361,7 @@ class _GatherRowsAD(torch.autograd.Function):
         idx, count = ctx.saved_tensors
         g = g.contiguous().float()
         dst = torch.zeros(ctx.n_rows, g.shape[1], device=g.device)
-        _lib.check(_lib.lib().lab4d_scatter_rows(_lib.ptr(g), _lib.ptr(idx), _lib.ptr(count), g.shape[0], g.shape[1], _lib.ptr(dst), _lib.stream()), "scatter_rows")
+        _lib.call("scatter_rows", g, idx, count, g.shape[0], g.shape[1], dst)
         return dst, None, None, None
 
 
@@ -389,7 +373,7 @@ class _ScatterRowsAD(torch.autograd.Function):
         src = src.contiguous().float()
         _lib.require_device(src, idx, count)
         dst = torch.zeros(int(n_rows), src.shape[1], device=src.device)
-        _lib.check(_lib.lib().lab4d_scatter_rows(_lib.ptr(src), _lib.ptr(idx), _lib.ptr(count), src.shape[0], src.shape[1], _lib.ptr(dst), _lib.stream()), "scatter_rows")
+        _lib.call("scatter_rows", src, idx, count, src.shape[0], src.shape[1], dst)
         ctx.save_for_backward(idx, count)
         ctx.cap = src.shape[0]
         return dst
@@ -399,7 +383,7 @@ class _ScatterRowsAD(torch.autograd.Function):
         idx, count = ctx.saved_tensors
         g = g.contiguous().float()
         out = torch.empty(ctx.cap, g.shape[1], device=g.device)
-        _lib.check(_lib.lib().lab4d_gather_rows(_lib.ptr(g), _lib.ptr(idx), _lib.ptr(count), ctx.cap, g.shape[1], _lib.ptr(out), _lib.stream()), "gather_rows")
+        _lib.call("gather_rows", g, idx, count, ctx.cap, g.shape[1], out)
         return out, None, None, None
 
 
@@ -418,13 +402,12 @@ def scatter_rows(src, idx, count, n_rows):
     """zeros (n_rows,C) with row idx[j] = src[j] for j < count (query_nerf's scatter into zeros, nerf.py:812-816)."""
     src = src.contiguous().float()
     out = torch.zeros(n_rows, src.shape[1], device=src.device)
-    _lib.check(_lib.lib().lab4d_scatter_rows(_lib.ptr(src), _lib.ptr(idx), _lib.ptr(count), src.shape[0], src.shape[1], _lib.ptr(out), _lib.stream()),
-               "scatter_rows")
+    _lib.call("scatter_rows", src, idx, count, src.shape[0], src.shape[1], out)
     return out
 
 
 @torch.no_grad()
 def frame_of(idx, count, spf):
     out = torch.empty_like(idx)
-    _lib.check(_lib.lib().lab4d_frame_of(_lib.ptr(idx), _lib.ptr(count), idx.numel(), int(spf), _lib.ptr(out), _lib.stream()), "frame_of")
+    _lib.call("frame_of", idx, count, idx.numel(), int(spf), out)
     return out

@@ -46,31 +46,31 @@ def _prog(spec, tensors, ins, outs, grads=None, acc=None):
     p = _Prog()
     p.n_layers, p.row_stride = len(spec["layers"]), spec["row_stride"]
     it = iter(range(len(tensors)))
-    g = (lambda i: _lib.ptr(grads[i]) if grads is not None and grads[i] is not None else None)
+    g = (lambda i: _lib.dp(grads[i]) if grads is not None and grads[i] is not None else None)
     ac = (lambda i: bool(acc is not None and acc[i]))
     for l, L in enumerate(spec["layers"]):
         q = p.layer[l]
         iw = next(it)
-        q.W, q.dW, a = _lib.ptr(tensors[iw]), g(iw), int(ac(iw))
+        q.W, q.dW, a = _lib.dp(tensors[iw]), g(iw), int(ac(iw))
         if L["bias"]:
             ib = next(it)
-            q.b, q.db = _lib.ptr(tensors[ib]), g(ib)
+            q.b, q.db = _lib.dp(tensors[ib]), g(ib)
             a |= 2 * int(ac(ib))
         q.in_dim, q.out_dim, q.src_col, q.dst_col, q.relu, q.acc = L["in_dim"], L["out_dim"], L["src"], L["dst"], int(L["relu"]), a
     t = spec.get("time")
     if t is not None:
-        p.frame_id, p.vstart, p.vidlen = _lib.ptr(t["frame_id"]), _lib.ptr(t["vstart"]), _lib.ptr(t["vidlen"])
-        p.vid = _lib.ptr(t["vid"]) if t["vid"] is not None else None
+        p.frame_id, p.vstart, p.vidlen = _lib.dp(t["frame_id"]), _lib.dp(t["vstart"]), _lib.dp(t["vidlen"])
+        p.vid = _lib.dp(t["vid"]) if t["vid"] is not None else None
         p.max_ts, p.time_scale, p.n_freq, p.four_col = float(t["max_ts"]), float(t["time_scale"]), int(t["n_freq"]), int(t["four_col"])
         if t["inst_dim"] > 0:
             ii = next(it)
-            p.inst_W, p.d_inst_W, p.acc_inst = _lib.ptr(tensors[ii]), g(ii), int(ac(ii))
+            p.inst_W, p.d_inst_W, p.acc_inst = _lib.dp(tensors[ii]), g(ii), int(ac(ii))
         p.inst_col, p.inst_dim, p.inst_rows = int(t["inst_col"]), int(t["inst_dim"]), int(t["inst_rows"])
     p.n_in, p.n_out = len(spec["inputs"]), len(spec["outs"])
     for q, ((c, w), x) in enumerate(zip(spec["inputs"], ins)):
-        p.inp[q].ptr, p.inp[q].col, p.inp[q].width = (_lib.ptr(x) if x is not None else None), c, w
+        p.inp[q].ptr, p.inp[q].col, p.inp[q].width = (_lib.dp(x) if x is not None else None), c, w
     for q, ((c, w), x) in enumerate(zip(spec["outs"], outs)):
-        p.out[q].ptr, p.out[q].col, p.out[q].width = (_lib.ptr(x) if x is not None else None), c, w
+        p.out[q].ptr, p.out[q].col, p.out[q].width = (_lib.dp(x) if x is not None else None), c, w
     return p
 
 
@@ -89,7 +89,7 @@ class _Run(Function):
         work = torch.empty(M, rs, device=dev)
         outs = [torch.empty(M, w, device=dev) for _, w in spec["outs"]]
         p = _prog(spec, params, ins, outs)
-        _lib.check(_lib.lib().lab4d_rowmlp_forward(ctypes.byref(p), _lib.ptr(work), M, _lib.stream()), "rowmlp_forward")
+        _lib.call("rowmlp_forward", ctypes.byref(p), work, M)
         ctx.spec, ctx.n_in, ctx.param_refs = spec, n_in, args[n_in:]
         ctx.save_for_backward(work, *params)
         return tuple(outs)
@@ -117,7 +117,7 @@ class _Run(Function):
                 gt = torch.empty_like(t)
                 grads.append(gt); acc.append(False); ret.append(gt)
         p = _prog(spec, params, gins, gos, grads, acc)
-        _lib.check(_lib.lib().lab4d_rowmlp_backward(ctypes.byref(p), _lib.ptr(work), _lib.ptr(gwork), M, _lib.stream()), "rowmlp_backward")
+        _lib.call("rowmlp_backward", ctypes.byref(p), work, gwork, M)
         return (None, None) + tuple(gins) + tuple(ret)
 
 

@@ -32,8 +32,7 @@ class BoneCoords(Function):
         S, (M, B) = xyz.shape[0], art_r.shape[:2]
         out = torch.empty(S, 3 * B, device=xyz.device)
         with _lib.timed("k_bone_fwd", (0.0, 4.0 * S * (3 + 3 * B))):  # algorithmic bytes: xyz read, (S,3B) written
-            _lib.check(_lib.lib().lab4d_bone_coords_forward(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), S, spf, M, B,
-                                                            _lib.ptr(out), _lib.stream()), "bone_coords_forward")
+            _lib.call("bone_coords_forward", xyz, art_r, art_d, gauss, S, spf, M, B, out)
         ctx.save_for_backward(xyz, art_r, art_d, gauss)
         ctx.spf = spf
         return out
@@ -56,12 +55,10 @@ def bone_coords_backward(saved, spf, need, g):
         # one pass over the (S,3B) gradient: the point gradient and the per-frame Gram matrix of the parameter path together
         G = torch.empty(M, 3 * B, 4, device=xyz.device)
         with _lib.timed("k_bone_bwd_x+gram", (2.0 * S * 3 * B * 4, 4.0 * S * (3 + 3 + 3 * B))):
-            _lib.check(_lib.lib().lab4d_bone_coords_backward_gram(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(gauss), _lib.ptr(g), S, spf, M, B,
-                                                                  _lib.ptr(gx), _lib.ptr(G), _lib.stream()), "bone_coords_backward_gram")
+            _lib.call("bone_coords_backward_gram", xyz, art_r, gauss, g, S, spf, M, B, gx, G)
     else:
         with _lib.timed("k_bone_bwd_x", (0.0, 4.0 * S * (3 + 3 * B))):
-            _lib.check(_lib.lib().lab4d_bone_coords_backward(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(g), S, spf,
-                                                             M, B, _lib.ptr(gx), None, None, None, _lib.stream()), "bone_coords_backward")
+            _lib.call("bone_coords_backward", xyz, art_r, art_d, gauss, g, S, spf, M, B, gx, None, None, None)
         # parameter gradients: out[s,b,:] = (R_b x_s + t_b) / gauss_b is affine in x_s, so every one of them is a function
         # of the per-frame Gram matrix G[m,b,k,j] = sum_{s in m} g[s,b,k] [x_s,1]_j: one tall-skinny product on the device
         if not any(need):
@@ -69,13 +66,12 @@ def bone_coords_backward(saved, spf, need, g):
         xh = torch.cat([xyz, torch.ones_like(xyz[:, :1])], -1)
         G = torch.zeros(M, 3 * B, 4, device=xyz.device)
         with _lib.timed("k_gram_pf_rb(bone)", (2.0 * S * 3 * B * 4, 4.0 * S * (3 * B + 4))):
-            _lib.check(_lib.lib().lab4d_gram_per_frame(_lib.ptr(g), 3 * B, _lib.ptr(xh), 4, S, spf, M, _lib.ptr(G), _lib.stream()), "gram_per_frame")
+            _lib.call("gram_per_frame", g, 3 * B, xh, 4, S, spf, M, G)
     # (M,B)-sized chain rule: one thread per (frame, bone) (csrc/skinning.hip k_bone_param_from_gram)
     gar = torch.empty_like(art_r) if need_r else None
     gad = torch.empty_like(art_d) if need_d else None
     gg = torch.zeros_like(gauss) if need_g else None
-    _lib.check(_lib.lib().lab4d_bone_params_from_gram(_lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(G), M, B, _lib.ptr(gar),
-                                                      _lib.ptr(gad), _lib.ptr(gg), _lib.stream()), "bone_params_from_gram")
+    _lib.call("bone_params_from_gram", art_r, art_d, gauss, G, M, B, gar, gad, gg)
     return gx, gar, gad, gg
 
 
@@ -85,7 +81,7 @@ def bone_affine(art_r, art_d, gauss):
     _lib.require_device(art_r, art_d, gauss)
     M, B = art_r.shape[:2]
     aff = torch.empty(M, 3 * B, 4, device=art_r.device)
-    _lib.check(_lib.lib().lab4d_bone_affine(_lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), M, B, _lib.ptr(aff), _lib.stream()), "bone_affine")
+    _lib.call("bone_affine", art_r, art_d, gauss, M, B, aff)
     return aff
 
 
@@ -137,8 +133,7 @@ class BoneAffine(Function):
         gad = torch.empty_like(art_d) if need_d else None
         gg = torch.zeros_like(gauss) if need_g else None
         if need_r or need_d or need_g:
-            _lib.check(_lib.lib().lab4d_bone_params_from_gram(_lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(G), M, B, _lib.ptr(gar),
-                                                              _lib.ptr(gad), _lib.ptr(gg), _lib.stream()), "bone_params_from_gram")
+            _lib.call("bone_params_from_gram", art_r, art_d, gauss, G, M, B, gar, gad, gg)
         return gar, gad, gg
 
 
@@ -195,9 +190,7 @@ class SkinBlend(Function):
         dsk = torch.empty(S, 1, device=xyz.device)
         work = torch.empty(M * B * 12, device=xyz.device)
         with _lib.timed("k_blend_fwd", (0.0, 4.0 * S * (3 + B + 3 + 2))):  # xyz + raw read; out, entropy, delta_skin written
-            _lib.check(_lib.lib().lab4d_skin_blend_forward(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(raw),
-                                                           _lib.ptr(se3_r), _lib.ptr(se3_d), S, spf, M, B, _lib.ptr(out), _lib.ptr(ent), _lib.ptr(dsk),
-                                                           _lib.ptr(work), _lib.stream()), "skin_blend_forward")
+            _lib.call("skin_blend_forward", xyz, art_r, art_d, gauss, raw, se3_r, se3_d, S, spf, M, B, out, ent, dsk, work)
         ctx.save_for_backward(xyz, raw, art_r, art_d, gauss, se3_r, se3_d)
         ctx.spf = spf
         return out, ent, dsk
@@ -220,10 +213,8 @@ class SkinBlend(Function):
         # one entry for the whole adjoint (k_blend_bwd incl. its two per-frame Gram reductions): reads xyz, raw, g_out, g_ent, g_dskin; writes
         # g_xyz, g_raw (unfused: also the (S, 2B+18) work arrays, which the Gram kernels read once more)
         with _lib.timed("k_blend_bwd+gram", (0.0, 4.0 * S * ((3 + B + 3 + 2) + (3 + B) + (0 if fused else 2 * (2 * B + 18))))):
-            _lib.check(_lib.lib().lab4d_skin_blend_backward(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(raw),
-                                                            _lib.ptr(se3_r), _lib.ptr(se3_d), _lib.ptr(g_out), _lib.ptr(g_ent), _lib.ptr(g_dsk), S,
-                                                            ctx.spf, M, B, _lib.ptr(gx), _lib.ptr(gr), _lib.ptr(gse3), _lib.ptr(gar), _lib.ptr(gad),
-                                                            _lib.ptr(gg), _lib.ptr(work), _lib.stream()), "skin_blend_backward")
+            _lib.call("skin_blend_backward", xyz, art_r, art_d, gauss, raw, se3_r, se3_d, g_out, g_ent, g_dsk, S, ctx.spf, M, B, gx, gr, gse3, gar, gad, gg,
+                      work)
         return gx, gr, gar, gad, gg, gse3[..., :4].contiguous(), gse3[..., 4:].contiguous(), None
 
 
@@ -247,9 +238,7 @@ class SkinBlendMulti(Function):
             dsk = torch.empty(S, 1, device=xyz.device)
             work = torch.empty(M * B * 12, device=xyz.device)
             with _lib.timed("k_blend_fwd", (0.0, 4.0 * S * (3 + B + 3 + 2))):
-                _lib.check(_lib.lib().lab4d_skin_blend_forward(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(raw),
-                                                               _lib.ptr(se3s[i]), _lib.ptr(se3s[i + 1]), S, spf, M, B, _lib.ptr(out), _lib.ptr(ent),
-                                                               _lib.ptr(dsk), _lib.ptr(work), _lib.stream()), "skin_blend_forward")
+                _lib.call("skin_blend_forward", xyz, art_r, art_d, gauss, raw, se3s[i], se3s[i + 1], S, spf, M, B, out, ent, dsk, work)
             outs += [out, ent, dsk]
         ctx.save_for_backward(xyz, raw, art_r, art_d, gauss, *se3s)
         ctx.spf = spf
@@ -282,11 +271,8 @@ class SkinBlendMulti(Function):
             pg = torch.zeros_like(gauss) if need_p else None
             work = work0 if first else _blend_bwd_work(S, ctx.spf, M, B, xyz.device)[0]
             with _lib.timed("k_blend_bwd+gram", (0.0, 4.0 * S * ((3 + B + 3 + 2) + (3 + B) * (1 if first else 2) + (0 if fused else 2 * (2 * B + 18))))):
-                _lib.check(_lib.lib().lab4d_skin_blend_backward_acc(_lib.ptr(xyz), _lib.ptr(art_r), _lib.ptr(art_d), _lib.ptr(gauss), _lib.ptr(raw),
-                                                                    _lib.ptr(se3s[i]), _lib.ptr(se3s[i + 1]), _lib.ptr(g_out), _lib.ptr(g_ent),
-                                                                    _lib.ptr(g_dsk), S, ctx.spf, M, B, _lib.ptr(gx), _lib.ptr(gr), _lib.ptr(gse3),
-                                                                    _lib.ptr(par), _lib.ptr(pad), _lib.ptr(pg), _lib.ptr(work), 0 if first else 1,
-                                                                    _lib.stream()), "skin_blend_backward_acc")
+                _lib.call("skin_blend_backward_acc", xyz, art_r, art_d, gauss, raw, se3s[i], se3s[i + 1], g_out, g_ent, g_dsk, S, ctx.spf, M, B, gx, gr, gse3,
+                          par, pad, pg, work, 0 if first else 1)
             first = False
             if need_p:  # (M,B)-sized: summed over the targets here
                 gar, gad, gg = (par, pad, pg) if gar is None else (gar + par, gad + pad, gg + pg)

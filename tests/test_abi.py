@@ -124,6 +124,88 @@ def test_data_pointer_parameters_take_host_arrays():
         ctypes.c_void_p.from_param(arg)
 
 
+def good_args(name):
+    """One valid argument per slot of lab4d_<name> (the stream left out): NULL for a pointer, 1 for an integer, 0.5 for a float."""
+    _, params, has_stream = _lib.SIGNATURES["lab4d_" + name]
+    return [0.5 if p is ctypes.c_float else None if p is ctypes.c_void_p or isinstance(p, str) else 1 for p in params[:len(params) - has_stream]]
+
+
+@pytest.mark.parametrize("name,n_args,pointer_at,int_at,float_at", [("hashsdf_forward", 13, 1, 3, None), ("adamw_step", 14, 2, 4, 8)])
+def test_marshal_checks_every_slot_against_the_prototype(name, n_args, pointer_at, int_at, float_at):
+    """_lib.marshal (the argument half of _lib.call) decides by include/*.h alone -- no library, no GPU: the count, a number where a pointer
+    belongs (c_void_p would pass it on as an address), a float or a tensor where an integer belongs, a host or strided tensor."""
+    import torch
+    good = good_args(name)
+    assert len(good) == n_args
+    out = _lib.marshal(name, good)
+    assert out == good and len(out) == len(_lib.SIGNATURES["lab4d_" + name][1]) - 1  # (the stream is call()'s to add)
+    proto = re.escape(_lib.prototype("lab4d_" + name))
+    assert proto.startswith("int\\ lab4d_" + name) and "stream" in proto
+    for bad in (good[:-1], good + [None]):
+        with pytest.raises(TypeError, match="takes %d arguments.*got %d.*%s" % (n_args, len(bad), proto)):
+            _lib.marshal(name, bad)
+
+    def put(at, value):
+        return good[:at] + [value] + good[at + 1:]
+    for number in (4096, 1.0, True):
+        with pytest.raises(TypeError, match=r"lab4d_%s: args\[%d\] must be a data pointer.*%s" % (name, pointer_at, proto)):
+            _lib.marshal(name, put(pointer_at, number))
+    with pytest.raises(TypeError, match=r"lab4d_%s: args\[%d\] must be an int" % (name, int_at)):
+        _lib.marshal(name, put(int_at, 2.0))
+    assert _lib.marshal(name, put(int_at, True))[int_at] is True
+    with pytest.raises(RuntimeError, match="got a cpu tensor -- there is no CPU path"):
+        _lib.marshal(name, put(pointer_at, torch.zeros(4)))
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        _lib.marshal(name, put(pointer_at, torch.zeros(4, 2)[:, 0]))
+    with pytest.raises(TypeError, match=r"args\[%d\] must be an int, got a int64 tensor" % int_at):  # (a 0-dim tensor here would be a hidden sync)
+        _lib.marshal(name, put(int_at, torch.tensor(3)))
+    if float_at is not None:
+        assert _lib.marshal(name, put(float_at, 2))[float_at] == 2
+        with pytest.raises(TypeError, match=r"args\[%d\] must be a number" % float_at):
+            _lib.marshal(name, put(float_at, torch.tensor(0.5)))
+    for host in (ctypes.c_void_p(64), (ctypes.c_float * 4)(), ctypes.byref(ctypes.c_int(0))):
+        assert _lib.marshal(name, put(pointer_at, host))[pointer_at] is host
+    with pytest.raises(RuntimeError, match="no entry point lab4d_%s_nope" % name):
+        _lib.marshal(name + "_nope", good)
+
+
+def test_marshal_takes_only_the_bound_mirror_in_a_struct_slot():
+    name, at = "packed_composite_backward", 2
+    assert _lib.SIGNATURES["lab4d_" + name][1][at] == "lab4d_field_list"
+    good = good_args(name)
+    fl = _lib.FieldList()
+    for ok in (fl, ctypes.byref(fl), ctypes.pointer(fl)):
+        ctypes.POINTER(_lib.FieldList).from_param(_lib.marshal(name, good[:at] + [ok] + good[at + 1:])[at])
+    for bad in (_lib.FieldGrads(), 64, ctypes.c_void_p(64)):
+        with pytest.raises(TypeError, match=r"args\[2\] must be a pointer to lab4d_field_list"):
+            _lib.marshal(name, good[:at] + [bad] + good[at + 1:])
+
+
+def test_every_call_site_names_a_prototype_and_counts_its_arguments():
+    """Census of the package's launch sites, without a GPU: every _lib.call("<name>", ...) names an entry point of include/*.h and, where it
+    spreads no list into the arguments, passes as many as the prototype has in front of its stream."""
+    import ast
+    sites = []
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "lab4d_amd")):
+        for f in files:
+            if not f.endswith(".py"):
+                continue
+            path = os.path.join(dirpath, f)
+            for node in ast.walk(ast.parse(open(path).read())):
+                if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "call"
+                        and isinstance(node.func.value, ast.Name) and node.func.value.id == "_lib"):
+                    first = node.args[0]
+                    names = [first] if isinstance(first, ast.Constant) else [first.body, first.orelse] if isinstance(first, ast.IfExp) else []
+                    assert names and all(isinstance(n, ast.Constant) and isinstance(n.value, str) for n in names), (path, node.lineno)
+                    sites += [(os.path.relpath(path, ROOT), node.lineno, n.value, node.args[1:]) for n in names]
+    assert len(sites) >= 85, len(sites)
+    for where, line, name, args in sites:
+        assert "lab4d_" + name in _lib.SIGNATURES, (where, line, name)
+        _, params, has_stream = _lib.SIGNATURES["lab4d_" + name]
+        if not any(isinstance(a, ast.Starred) for a in args):
+            assert len(args) == len(params) - has_stream, (where, line, name, _lib.prototype("lab4d_" + name))
+
+
 def test_timed_entry_points_are_the_ones_with_a_stream(so):
     """_ProfiledLib times a function iff its prototype has a `stream` parameter: no size query, no getter."""
     timed_names = set()

@@ -439,6 +439,32 @@ def test_profile_times_the_launch_and_not_the_size_query():
     assert int(count) == int(mask.sum()) and torch.equal(idx.cpu()[: int(count)], torch.nonzero(mask).flatten().int())
 
 
+def test_checked_call_launches_what_the_op_launches_and_refuses_on_the_host():
+    """_lib.call marshals by the parsed prototype: given the tensors themselves it launches what deformable.volsdf_density launches (the same bits,
+    n = 65: one wave plus one), and a strided view or a Python int in a data-pointer slot is refused before anything is launched -- the output
+    keeps its fill and the profile gets no entry."""
+    from lab4d_amd import _lib, deformable as DF
+    n = 65
+    sdf = (torch.randn(n, generator=gen(78)) * 0.1).to(DEV)
+    logibeta = torch.tensor([2.3], device=DEV)
+    ib = logibeta.exp().reshape(1).contiguous().float()
+    out = torch.full((n,), -7.0, device=DEV)
+    _lib.call("volsdf_forward", sdf, ib, n, out)
+    assert torch.equal(out, DF.volsdf_density(sdf, logibeta))
+    out.fill_(-7.0)
+    _lib.PROF = {}
+    try:
+        with pytest.raises(RuntimeError, match="lab4d_amd ops need contiguous tensors"):
+            _lib.call("volsdf_forward", sdf[::2], ib, n, out)  # (a view into sdf's own n floats)
+        with pytest.raises(TypeError, match=r"lab4d_volsdf_forward: args\[0\]"):
+            _lib.call("volsdf_forward", n, ib, n, out)
+        torch.cuda.synchronize()
+        assert _lib.prof_summary() == {}
+    finally:
+        _lib.PROF = None
+    assert bool((out == -7.0).all())
+
+
 def test_valid_mask_is_bit_exact_at_the_box_faces():
     """check_inside_aabb uses strict inequalities (geom_utils.py:506-517): points exactly on a face are outside."""
     from lab4d_amd import render_utils as RU

@@ -51,7 +51,7 @@ def test_grad_norm_at_scale():
     n = (1 << 24) + 3
     x = torch.randn(n, device=DEV)
     work, norm, coef = torch.empty(512, device=DEV), torch.zeros(1, device=DEV), torch.zeros(1, device=DEV)
-    _lib.check(_lib.lib().lab4d_grad_norm_clip(_lib.ptr(x), n, 5.0, _lib.ptr(work), _lib.ptr(norm), _lib.ptr(coef), _lib.stream()), "grad_norm_clip")
+    _lib.call("grad_norm_clip", x, n, 5.0, work, norm, coef)
     ref = float(x.double().norm())
     assert abs(float(norm) - ref) <= 1e-5 * ref
     assert abs(float(coef) - min(1.0, 5.0 / (ref + 1e-6))) <= 1e-5

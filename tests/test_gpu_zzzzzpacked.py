@@ -166,8 +166,7 @@ def test_composite_weights_and_transmittance_outputs():
     w, T = torch.zeros(case["P"], device=DEV), torch.zeros(case["P"], device=DEV)
     mask, out = torch.empty(case["R"], device=DEV), torch.empty(case["R"], 3, device=DEV)
     fl, _ = packed._field_list([f], [0])
-    _lib.check(_lib.lib().lab4d_packed_composite_forward(_lib.ptr(density), _lib.ptr(deltas), fl, _lib.ptr(start), _lib.ptr(count), case["R"], case["P"],
-                                                         _lib.ptr(w), _lib.ptr(T), _lib.ptr(mask), _lib.ptr(out), _lib.stream()), "packed_composite_forward")
+    _lib.call("packed_composite_forward", density, deltas, fl, start, count, case["R"], case["P"], w, T, mask, out)
     assert PC.rel_max(w.cpu().numpy(), ref["weights"]) < PC.FP32_BAR and PC.rel_max(T.cpu().numpy(), ref["transmit"]) < PC.FP32_BAR
     assert PC.rel_max(mask.cpu().numpy(), ref["mask"]) < PC.FP32_BAR
 

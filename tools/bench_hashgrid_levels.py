@@ -33,8 +33,7 @@ for l, r in enumerate(levels):
         for rep in range(3):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            _lib.check(_lib.lib().lab4d_hashgrid_backward(_lib.ptr(x01), _lib.ptr(table), _lib.ptr(rt), _lib.ptr(g), S, 1, log2_T, F, _lib.ptr(a_gt), _lib.ptr(a_gx),
-                                                          _lib.stream()), "hashgrid_backward")
+            _lib.call("hashgrid_backward", x01, table, rt, g, S, 1, log2_T, F, a_gt, a_gx)
             e1.record()
             torch.cuda.synchronize()
             ms[what] = round(e0.elapsed_time(e1), 3)

@@ -129,15 +129,12 @@ def main():
     gf = _lib.FieldGrads()
     gf.n_fields = 2
     gf.fields[0], gf.fields[1] = _lib.dp(g_rgb), None  # (the gradients render_packed asks for: density and colour)
-    L, ptr = _lib.lib(), _lib.ptr
 
     def comp_fwd():
-        _lib.check(L.lab4d_packed_composite_forward(ptr(dens), ptr(rays.deltas), fl, ptr(rays.ray_start), ptr(rays.ray_count), R, cap, None, None,
-                                                    ptr(c_mask), ptr(c_out), _lib.stream()), "packed_composite_forward")
+        _lib.call("packed_composite_forward", dens, rays.deltas, fl, rays.ray_start, rays.ray_count, R, cap, None, None, c_mask, c_out)
 
     def comp_bwd():
-        _lib.check(L.lab4d_packed_composite_backward(ptr(dens), ptr(rays.deltas), fl, ptr(rays.ray_start), ptr(rays.ray_count), R, cap, ptr(g_mask),
-                                                     ptr(g_out), ptr(g_dens), None, gf, _lib.stream()), "packed_composite_backward")
+        _lib.call("packed_composite_backward", dens, rays.deltas, fl, rays.ray_start, rays.ray_count, R, cap, g_mask, g_out, g_dens, None, gf)
 
     result = {
         "workload": "forward + backward of one chunk of the hash configuration: %d rays x %d candidates (%d lattice points), ball field, bf16 chains, "

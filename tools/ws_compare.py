@@ -75,7 +75,7 @@ def run_fwd(c, ws):
     r["out"] = torch.zeros(S, d.c_out, device="cuda")
     a.out = _lib.dp(r["out"])
     r["args"] = a
-    _lib.check(_lib.lib().lab4d_mlp_forward(ctypes.byref(a), _lib.stream()), "mlp_forward")
+    _lib.call("mlp_forward", ctypes.byref(a))
     torch.cuda.synchronize()
     return r
 
@@ -110,7 +110,7 @@ def run_bwd(c, f, ws):
         r["d_x"] = torch.zeros(S, 3, device="cuda")
         a.d_x = _lib.dp(r["d_x"])
     r["args"] = a
-    _lib.check(_lib.lib().lab4d_mlp_backward(ctypes.byref(a), _lib.stream()), "mlp_backward")
+    _lib.call("mlp_backward", ctypes.byref(a))
     torch.cuda.synchronize()
     return r
 
@@ -136,7 +136,7 @@ def run_tangent(c, f, ws):
     r["out"] = torch.zeros(S, d.c_out, device="cuda")
     a.out = _lib.dp(r["out"])
     r["args"] = a
-    _lib.check(_lib.lib().lab4d_mlp_forward_tangent(ctypes.byref(a), _lib.stream()), "mlp_forward_tangent")
+    _lib.call("mlp_forward_tangent", ctypes.byref(a))
     torch.cuda.synchronize()
     return r
 
