@@ -117,26 +117,32 @@ def _declarations(text):
         yield ret, name, params, "%s %s(%s)" % (ret.strip(), name, " ".join(params.split()))
 
 
+def parse_parameters(params, where, proto):
+    """The parameter text of one C function -> a list with a ctypes scalar type, c_void_p for a data pointer, or the C NAME of a lab4d_* struct
+    for a pointer to one (argtypes() gives it its type).  A type outside _SCALARS raises: there is no default.  (The one copy of this rule:
+    tests/host_twin.py reads the CPU twins' definitions with it.)"""
+    args = []
+    for p in [] if params.strip() in ("", "void") else params.split(","):
+        words = [w for w in p.replace("*", " * ").split() if w != "const"]
+        if "*" in words:
+            args.append(words[0] if words[0].startswith("lab4d_") else vp)
+        else:  # `<type> <name>` or a bare `<type>`
+            key = " ".join(words) if " ".join(words) in _SCALARS else " ".join(words[:-1])
+            if key not in _SCALARS:
+                raise TypeError("%s: parameter '%s' of `%s` is neither a pointer nor one of %s" % (where, p.strip(), proto, sorted(_SCALARS)))
+            args.append(_SCALARS[key])
+    return args
+
+
 def parse_prototypes(text, where):
-    """C header text -> {name: (restype, params, has_stream)} for every `<return type> lab4d_<name>(<params>);` in it.  A parameter is a ctypes
-    scalar type, c_void_p for a data pointer, or the C NAME of a lab4d_* struct for a pointer to one (argtypes() gives it its type).  A type
-    outside the closed maps above raises: there is no default."""
+    """C header text -> {name: (restype, params, has_stream)} for every `<return type> lab4d_<name>(<params>);` in it, the parameters as
+    parse_parameters gives them.  A return type outside _RETURNS raises as well."""
     out = {}
     for ret, name, params, proto in _declarations(text):
         ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
         if ret not in _RETURNS:
             raise TypeError("%s: return type '%s' of `%s` is not one of %s" % (where, ret, proto, sorted(_RETURNS)))
-        args = []
-        for p in [] if params.strip() in ("", "void") else params.split(","):
-            words = [w for w in p.replace("*", " * ").split() if w != "const"]
-            if "*" in words:
-                args.append(words[0] if words[0].startswith("lab4d_") else vp)
-            else:  # `<type> <name>` or a bare `<type>`
-                key = " ".join(words) if " ".join(words) in _SCALARS else " ".join(words[:-1])
-                if key not in _SCALARS:
-                    raise TypeError("%s: parameter '%s' of `%s` is neither a pointer nor one of %s" % (where, p.strip(), proto, sorted(_SCALARS)))
-                args.append(_SCALARS[key])
-        out[name] = (_RETURNS[ret], args, bool(re.search(r"\bstream\s*(,|$)", params)))
+        out[name] = (_RETURNS[ret], parse_parameters(params, where, proto), bool(re.search(r"\bstream\s*(,|$)", params)))
     return out
 
 

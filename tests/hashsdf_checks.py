@@ -2,18 +2,14 @@
 harness of the hash field's SDF gradient (tests/host_harness/hashsdf_host.cpp over lab4d_amd/csrc/hashsdf_math.hpp), the test inputs, and
 the truth: float64 torch autograd on the CPU over oracle/hashgrid_oracle.py -- hash_encode, the two Linears, autograd.grad(create_graph=True)
 for the gradient in the point, a second autograd.grad for the parameter gradients.  Nothing of the code under test enters the truth."""
-import ctypes
 import functools
-import os
-import subprocess
 
 import numpy as np
 import torch
 
+import host_twin
 from oracle import hashgrid_oracle as HO
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "tests", "host_harness")
 TOL = 1e-4  # relative L2 per tensor: the project's fp32 bar (README.md)
 CONFIGS = {"a": {"L": 16, "F": 2, "n_min": 4, "n_max": 128, "log2_T": 12},   # levels 0-5 dense, 6-15 hashed with heavy collisions
            "b": {"L": 16, "F": 2, "n_min": 16, "n_max": 512, "log2_T": 14}}
@@ -22,33 +18,8 @@ NEAR = 1e-4      # points with x01 * res_l within this of an integer are dropped
 MAX_DROP = 0.02
 
 
-def _build_dir():
-    out = os.path.join(HARNESS, "_build")
-    os.makedirs(out, exist_ok=True)
-    return out
-
-
-@functools.lru_cache(None)
 def build_host():
-    so = os.path.join(_build_dir(), "hashsdf_host.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"),
-                           os.path.join(HARNESS, "hashsdf_host.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
-    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-    lib.hashsdf_host_forward.argtypes = [vp, vp, vp, cl, ci, ci, ci] + [vp] * 6
-    lib.hashsdf_host_backward.argtypes = [vp, vp, vp, cl, ci, ci, ci] + [vp] * 10 + [ci]
-    lib.hashsdf_host_forward.restype = lib.hashsdf_host_backward.restype = ci
-    return lib
-
-
-def build_sanitized_main():
-    """tests/host_harness/hashsdf_host_main.cpp with AddressSanitizer and UndefinedBehaviorSanitizer: a stand-alone program, run as a child
-    process (the runtimes are linked statically: the program needs nothing from its environment)"""
-    exe = os.path.join(_build_dir(), "hashsdf_host_main_asan")
-    subprocess.check_call(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-                           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"), "-I", HARNESS,
-                           os.path.join(HARNESS, "hashsdf_host_main.cpp"), "-o", exe])
-    return exe
+    return host_twin.load("hashsdf")
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// CPU build of lab4d_amd/csrc/fk_math.hpp for the test-suite (g++ -shared): the same row arithmetic the gfx950 kernels of
+// CPU build of lab4d_amd/csrc/fk_math.hpp for the test-suite (tests/host_twin.py): the same row arithmetic the gfx950 kernels of
 // fk.hip execute, callable from ctypes, so the `-m "not gpu"` tests can hold it to the oracle and to the reference fixture.
 // TEST INFRASTRUCTURE ONLY: never loaded by lab4d_amd/.
 #include "fk_math.hpp"

@@ -1,6 +1,6 @@
 // CPU twin of lab4d_amd/csrc/hashsdf.hip: serial loops over the SAME functions (csrc/hashsdf_math.hpp) with the layout of
 // include/lab4d_hashsdf.h, the adjoint in the kernel's order (workgroup b takes the tiles b, b + n_rows, ...; one partial row per
-// workgroup; rows folded ascending).  Built by tests/hashsdf_checks.py with g++ -ffp-contract=off; tests/test_hashsdf_host.py holds it to
+// workgroup; rows folded ascending).  Built by tests/host_twin.py with g++ -ffp-contract=off; tests/test_hashsdf_host.py holds it to
 // float64 autograd over oracle/hashgrid_oracle.py.  Returns 0, or -1 for sizes outside the contract.
 #include <stdint.h>
 

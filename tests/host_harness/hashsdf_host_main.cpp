@@ -1,4 +1,4 @@
-// Stand-alone run of the hash-SDF twin (hashsdf_host.cpp) for the sanitizers: tests/test_hashsdf_host.py builds this file with
+// Stand-alone run of the hash-SDF twin (hashsdf_host.cpp) for the sanitizers: tests/host_twin.py builds this file with
 // g++ -fsanitize=address,undefined and runs it as a child process.  Every buffer is a heap block of exactly the size the contract names
 // (include/lab4d_hashsdf.h), so a table entry gathered through an index past its level, or an output written past S, is an error report
 // and a non-zero exit.  It covers the special points of the rules: x01 exactly 0 and exactly 1, a point outside the box, a NaN point, 64

@@ -1,5 +1,5 @@
 // CPU twin of lab4d_amd/csrc/mesh.hip: a serial loop over grid points using the SAME per-cell functions (csrc/mesh_math.hpp) and the SAME
-// case table (csrc/mc_tables.hpp), with the ordering contract of include/lab4d_mesh.h.  Built by tests/test_mesh_host.py with
+// case table (csrc/mc_tables.hpp), with the ordering contract of include/lab4d_mesh.h.  Built by tests/host_twin.py with
 // g++ -ffp-contract=off; the GPU suite holds the kernels bit for bit to it (tests/test_gpu_zzzmesh.py).
 #include <stdint.h>
 

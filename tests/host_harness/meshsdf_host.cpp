@@ -1,5 +1,5 @@
 // CPU twin of lab4d_amd/csrc/meshsdf.hip: serial loops over the SAME functions (csrc/meshsdf_math.hpp) with the layout of
-// include/lab4d_meshsdf.h.  Built by tests/meshsdf_checks.py with g++ -ffp-contract=off; tests/test_meshsdf_host.py pins it against numpy
+// include/lab4d_meshsdf.h.  Built by tests/host_twin.py with g++ -ffp-contract=off; tests/test_meshsdf_host.py pins it against numpy
 // in float64, the GPU suite holds the kernels' distance, face and closest point bit for bit to it (tests/test_gpu_zzzzzzmeshsdf.py).
 #include <stdint.h>
 

@@ -1,4 +1,4 @@
-// Stand-alone run of the mesh-distance twin (meshsdf_host.cpp) for the sanitizers: tests/test_meshsdf_host.py builds this file with
+// Stand-alone run of the mesh-distance twin (meshsdf_host.cpp) for the sanitizers: tests/host_twin.py builds this file with
 // g++ -fsanitize=address,undefined and runs it as a child process.  Every buffer is a heap block of exactly the size the contract names
 // (include/lab4d_meshsdf.h), so a vertex gathered through an index that is out of range, or an output written past n_pts, is an error
 // report and a non-zero exit.  It covers the edge cases of the rules: degenerate triangles and out-of-range indices among valid ones,

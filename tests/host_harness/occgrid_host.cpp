@@ -1,5 +1,5 @@
 // CPU twin of lab4d_amd/csrc/occgrid.hip: serial loops over the SAME functions (csrc/occgrid_math.hpp) with the layout of
-// include/lab4d_occgrid.h.  Built by tests/occgrid_checks.py with g++ -ffp-contract=off; tests/test_occgrid_host.py pins it against
+// include/lab4d_occgrid.h.  Built by tests/host_twin.py with g++ -ffp-contract=off; tests/test_occgrid_host.py pins it against
 // numpy in float64, the GPU suite holds the kernels bit for bit to it (tests/test_gpu_zzzzoccgrid.py).
 #include <stdint.h>
 

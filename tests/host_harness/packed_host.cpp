@@ -1,5 +1,5 @@
 // CPU twin of lab4d_amd/csrc/packed.hip: serial loops over the SAME functions (csrc/packed_math.hpp over csrc/occgrid_math.hpp) with the
-// layout of include/lab4d_packed.h.  Built by tests/packed_checks.py with g++ -ffp-contract=off; tests/test_packed_host.py pins it against
+// layout of include/lab4d_packed.h.  Built by tests/host_twin.py with g++ -ffp-contract=off; tests/test_packed_host.py pins it against
 // numpy / torch in float64, the GPU suite holds the march kernels word for word to it (tests/test_gpu_zzzzzpacked.py).
 #include <stdint.h>
 

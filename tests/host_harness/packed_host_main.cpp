@@ -1,4 +1,4 @@
-// Stand-alone run of the packed twin (packed_host.cpp) for the sanitizers: tests/test_packed_host.py builds this file with
+// Stand-alone run of the packed twin (packed_host.cpp) for the sanitizers: tests/host_twin.py builds this file with
 // g++ -fsanitize=address,undefined and runs it as a child process.  Every buffer is a heap block of exactly the size the contract names
 // (include/lab4d_packed.h), so a row written past the capacity, or a read past a ray's rows, is an error report and a non-zero exit.  It
 // covers the truncation cases (cap = total, total - 1, 0) and rays without samples, on a small grid; the values are checked elsewhere.

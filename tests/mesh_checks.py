@@ -2,12 +2,12 @@
 the test volumes, and the properties every correct welded iso-surface has.  No skimage exists here to compare with, so the mesh is pinned
 by those properties (closed, manifold, consistently oriented, right Euler characteristic, vertices on the surface within the derived
 interpolation bound) and by the ordering contract of include/lab4d_mesh.h restated independently in numpy."""
-import ctypes
 import importlib.util
 import os
-import subprocess
 
 import numpy as np
+
+import host_twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,18 +31,7 @@ def gen_module():
 
 
 def build_host():
-    out = os.path.join(ROOT, "tests", "host_harness", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "mesh_host.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_harness", "mesh_host.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
-    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-    lib.mesh_host_extract.argtypes = [vp, vp, ci, ci, ci, ctypes.c_float, vp, vp, vp, cl, cl, vp]
-    lib.mesh_host_extract.restype = None
-    lib.mesh_host_largest_component.argtypes = [vp, vp, ci, ci, vp, vp, vp]
-    lib.mesh_host_largest_component.restype = None
-    return lib
+    return host_twin.load("mesh")
 
 
 def host_extract(lib, sdf, mask=None, level=0.0, origin=None, step=None):

@@ -1,47 +1,17 @@
 """Shared by tests/test_meshsdf_host.py (CPU twin against float64) and tests/test_gpu_zzzzzzmeshsdf.py (kernels against the twin): the host
 harness of the mesh distance (tests/host_harness/meshsdf_host.cpp over lab4d_amd/csrc/meshsdf_math.hpp), the test meshes, and the rules
 of include/lab4d_meshsdf.h restated in numpy float64: the same region classification, the same winding formula."""
-import ctypes
 import functools
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "tests", "host_harness")
+import host_twin
+
 EPS32 = float(np.finfo(np.float32).eps)
 
 
-def _build_dir():
-    out = os.path.join(HARNESS, "_build")
-    os.makedirs(out, exist_ok=True)
-    return out
-
-
-@functools.lru_cache(None)
 def build_host():
-    so = os.path.join(_build_dir(), "meshsdf_host.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"),
-                           os.path.join(HARNESS, "meshsdf_host.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
-    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-    lib.meshsdf_host_query.argtypes = [vp, vp, ci, ci, vp, cl] + [vp] * 5
-    lib.meshsdf_host_query_sliced.argtypes = [vp, vp, ci, ci, vp, cl, ci] + [vp] * 5
-    lib.meshsdf_host_valid.argtypes = [vp, vp, ci, ci, vp]
-    for f in (lib.meshsdf_host_query, lib.meshsdf_host_query_sliced, lib.meshsdf_host_valid):
-        f.restype = None
-    return lib
-
-
-def build_sanitized_main():
-    """tests/host_harness/meshsdf_host_main.cpp with AddressSanitizer and UndefinedBehaviorSanitizer: a stand-alone program, run as a child
-    process (the runtimes are linked statically: the program needs nothing from its environment)"""
-    exe = os.path.join(_build_dir(), "meshsdf_host_main_asan")
-    subprocess.check_call(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan",
-                           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"), "-I", HARNESS,
-                           os.path.join(HARNESS, "meshsdf_host_main.cpp"), "-o", exe])
-    return exe
+    return host_twin.load("meshsdf")
 
 
 def host_query(lib, verts, faces, pts, n_slices=None):

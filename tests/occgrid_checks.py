@@ -1,11 +1,11 @@
 """Shared by tests/test_occgrid_host.py (CPU twin against numpy in float64) and tests/test_gpu_zzzzoccgrid.py (kernels against the twin,
 bit for bit): the host harness of the occupancy grid (tests/host_harness/occgrid_host.cpp over lab4d_amd/csrc/occgrid_math.hpp), the
 test inputs, and the rules of include/lab4d_occgrid.h restated in numpy float64 (vectorised; shares no code with the header)."""
-import ctypes
 import os
-import subprocess
 
 import numpy as np
+
+import host_twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -15,20 +15,7 @@ MARGIN = 1e-4  # of a cell edge: where the float32 rule and the float64 rule may
 
 
 def build_host():
-    out = os.path.join(ROOT, "tests", "host_harness", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "occgrid_host.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_harness", "occgrid_host.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
-    vp, ci, cl, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
-    lib.occgrid_host_init.argtypes = [vp, vp, vp, ci]
-    lib.occgrid_host_update.argtypes = [vp, vp, vp, vp, ci, cf, cf]
-    lib.occgrid_host_mask.argtypes = [vp, vp, vp, ci, cl, vp]
-    lib.occgrid_host_ray_span.argtypes = [vp, vp, vp, vp, vp, ci, cl, vp, vp, vp]
-    for f in (lib.occgrid_host_init, lib.occgrid_host_update, lib.occgrid_host_mask, lib.occgrid_host_ray_span):
-        f.restype = None
-    return lib
+    return host_twin.load("occgrid")
 
 
 def n_words(G):

@@ -3,50 +3,21 @@ harness of packed marching / compositing (tests/host_harness/packed_host.cpp ove
 rules of include/lab4d_packed.h restated in float64 (numpy for the march; the oracle's compute_weights / integrate with torch autograd for
 the compositing).  The grid, ray and occupancy helpers are those of tests/occgrid_checks.py."""
 import ctypes
-import functools
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_twin  # noqa: E402
 import occgrid_checks as OC  # noqa: E402
 
 ROOT = OC.ROOT
-HARNESS = os.path.join(ROOT, "tests", "host_harness")
 FP32_BAR = 1e-4  # the project's fp32 bar (README): max-norm error relative to the reference's max-norm
 
 
-def _build_dir():
-    out = os.path.join(HARNESS, "_build")
-    os.makedirs(out, exist_ok=True)
-    return out
-
-
-@functools.lru_cache(None)
 def build_host():
-    so = os.path.join(_build_dir(), "packed_host.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"),
-                           os.path.join(HARNESS, "packed_host.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
-    vp, ci, cl, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
-    lib.packed_host_march_count.argtypes = [vp] * 5 + [ci, cl, cf, ci, vp]
-    lib.packed_host_march_write.argtypes = [vp] * 5 + [ci, cl, cf, ci, vp, cl] + [vp] * 8
-    lib.packed_host_composite_forward.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, cl, cl, vp, vp, vp, vp]
-    lib.packed_host_composite_backward.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, cl, cl, vp, vp, vp, vp, vp]
-    for f in (lib.packed_host_march_count, lib.packed_host_march_write, lib.packed_host_composite_forward, lib.packed_host_composite_backward):
-        f.restype = None
-    return lib
-
-
-def build_sanitized_main():
-    """tests/host_harness/packed_host_main.cpp with AddressSanitizer and UndefinedBehaviorSanitizer: a stand-alone program, run as a child process
-    (the runtimes are linked statically: the program needs nothing from its environment)"""
-    exe = os.path.join(_build_dir(), "packed_host_main_asan")
-    subprocess.check_call(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                           "-I", os.path.join(ROOT, "lab4d_amd", "csrc"), "-I", HARNESS, os.path.join(HARNESS, "packed_host_main.cpp"), "-o", exe])
-    return exe
+    return host_twin.load("packed")
 
 
 def _c(a, dt):

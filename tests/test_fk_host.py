@@ -3,25 +3,17 @@
 CPU only: this checks the math the gfx950 kernels execute without needing a GPU; tests/test_gpu_zpose.py runs the kernels."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F32 = ctypes.POINTER(ctypes.c_float)
-I32 = ctypes.POINTER(ctypes.c_int)
+import host_twin
 
 
 @pytest.fixture(scope="module")
 def host():
-    out = os.path.join(ROOT, "tests", "host_harness", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "fk_host.so")
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_harness", "fk_host.cpp"), "-o", so])
-    return ctypes.CDLL(so)
+    return host_twin.load("fk")
 
 
 @pytest.fixture(scope="module")
@@ -29,12 +21,8 @@ def pose(golden_dir):
     return torch.load(os.path.join(golden_dir, "pose.pt"), weights_only=False)
 
 
-def fp(a):
-    return a.ctypes.data_as(F32)
-
-
-def ip(a):
-    return a.ctypes.data_as(I32)
+def dp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)  # (holds a reference to `a`: a temporary array lives until the call returns)
 
 
 def arr(t):
@@ -60,16 +48,16 @@ def test_fk_rows_match_the_reference(host, pose):
     R, B = so3.shape[:2]
     order, parent = skel_arrays(edges, B)
     qr, qd = np.empty((R, B, 4), np.float32), np.empty((R, B, 4), np.float32)
-    host.fk_host_forward(fp(so3), fp(local), None, ip(order), ip(parent), R, B, 0, fp(qr), fp(qd))
+    host.fk_host_forward(dp(so3), dp(local), None, dp(order), dp(parent), R, B, 0, dp(qr), dp(qd))
     assert relerr(qr, fk["joints_dq"][0]) < 1e-5 and relerr(qd, fk["joints_dq"][1]) < 1e-5
     c = [arr(x) for x in fk["cot"]]
     g_so3, g_loc, g_sh = np.empty_like(so3), np.empty_like(local), np.empty((R, 3), np.float32)
-    host.fk_host_backward(fp(so3), fp(local), None, ip(order), ip(parent), fp(c[0]), fp(c[1]), R, B, 0, fp(g_so3), fp(g_loc), fp(g_sh))
+    host.fk_host_backward(dp(so3), dp(local), None, dp(order), dp(parent), dp(c[0]), dp(c[1]), R, B, 0, dp(g_so3), dp(g_loc), dp(g_sh))
     assert relerr(g_so3, fk["g_joints"][0]) < 1e-4 and relerr(g_loc, fk["g_joints"][1]) < 1e-4
     # + shift_joints_to_bones_dq
-    host.fk_host_forward(fp(so3), fp(local), fp(shift), ip(order), ip(parent), R, B, 1, fp(qr), fp(qd))
+    host.fk_host_forward(dp(so3), dp(local), dp(shift), dp(order), dp(parent), R, B, 1, dp(qr), dp(qd))
     assert relerr(qr, fk["bones_dq"][0]) < 1e-5 and relerr(qd, fk["bones_dq"][1]) < 1e-5
-    host.fk_host_backward(fp(so3), fp(local), fp(shift), ip(order), ip(parent), fp(c[2]), fp(c[3]), R, B, 1, fp(g_so3), fp(g_loc), fp(g_sh))
+    host.fk_host_backward(dp(so3), dp(local), dp(shift), dp(order), dp(parent), dp(c[2]), dp(c[3]), R, B, 1, dp(g_so3), dp(g_loc), dp(g_sh))
     assert relerr(g_so3, fk["g_bones"][0]) < 1e-4 and relerr(g_loc, fk["g_bones"][1]) < 1e-4
     assert relerr(g_sh.sum(0), fk["g_bones"][2]) < 1e-4
 
@@ -100,11 +88,11 @@ def test_skel_rows_match_the_oracle(host, pose):
         symm = np.asarray(skel["symm_idx"], dtype=np.int32)
         a_so3, a_ll, a_rest, a_sh = arr(so3), arr(ll), arr(rest_local), arr(shift)
         qr, qd = np.empty((R, B, 4), np.float32), np.empty((R, B, 4), np.float32)
-        host.skel_host_forward(fp(a_so3), fp(a_ll), ctypes.c_float(float(ls.detach())), fp(a_rest), fp(a_sh), ip(order), ip(parent), ip(symm), R, B, fp(qr), fp(qd))
+        host.skel_host_forward(dp(a_so3), dp(a_ll), float(ls.detach()), dp(a_rest), dp(a_sh), dp(order), dp(parent), dp(symm), R, B, dp(qr), dp(qd))
         assert relerr(qr, br.detach()) < 1e-5 and relerr(qd, bd.detach()) < 1e-5
         g_so3, g_ll, g_ls, g_sh = np.empty_like(a_so3), np.empty_like(a_ll), np.empty(R, np.float32), np.empty((R, 3), np.float32)
-        host.skel_host_backward(fp(a_so3), fp(a_ll), ctypes.c_float(float(ls.detach())), fp(a_rest), fp(a_sh), ip(order), ip(parent), ip(symm), fp(arr(c0)),
-                                fp(arr(c1)), R, B, fp(g_so3), fp(g_ll), fp(g_ls), fp(g_sh))
+        host.skel_host_backward(dp(a_so3), dp(a_ll), float(ls.detach()), dp(a_rest), dp(a_sh), dp(order), dp(parent), dp(symm), dp(arr(c0)),
+                                dp(arr(c1)), R, B, dp(g_so3), dp(g_ll), dp(g_ls), dp(g_sh))
         assert relerr(g_so3, ref[0]) < 1e-4 and relerr(g_ll, ref[1]) < 1e-4
         assert relerr(g_ls.sum(), ref[2]) < 1e-4 and relerr(g_sh.sum(0), ref[3]) < 1e-4
 
@@ -141,11 +129,11 @@ def test_fk_rows_on_random_trees(host):
         a_so3, a_loc = arr(so3), arr(local)
         a_sh = arr(shift) if bones else None
         qr, qd = np.empty((R, B, 4), np.float32), np.empty((R, B, 4), np.float32)
-        host.fk_host_forward(fp(a_so3), fp(a_loc), fp(a_sh) if bones else None, ip(order), ip(parent), R, B, int(bones), fp(qr), fp(qd))
+        host.fk_host_forward(dp(a_so3), dp(a_loc), dp(a_sh) if bones else None, dp(order), dp(parent), R, B, int(bones), dp(qr), dp(qd))
         assert np.allclose(qr, dq[0].detach().numpy(), atol=2e-5) and np.allclose(qd, dq[1].detach().numpy(), atol=2e-5)
         g_so3, g_loc, g_sh = np.empty_like(a_so3), np.empty_like(a_loc), np.empty((R, 3), np.float32)
-        host.fk_host_backward(fp(a_so3), fp(a_loc), fp(a_sh) if bones else None, ip(order), ip(parent), fp(arr(c0)), fp(arr(c1)), R, B, int(bones),
-                              fp(g_so3), fp(g_loc), fp(g_sh))
+        host.fk_host_backward(dp(a_so3), dp(a_loc), dp(a_sh) if bones else None, dp(order), dp(parent), dp(arr(c0)), dp(arr(c1)), R, B, int(bones),
+                              dp(g_so3), dp(g_loc), dp(g_sh))
         scale = max(1.0, float(ref[0].abs().max()))
         assert np.allclose(g_so3, ref[0].numpy(), atol=3e-4 * scale), float(np.abs(g_so3 - ref[0].numpy()).max())
         assert np.allclose(g_loc, ref[1].numpy(), atol=3e-4 * max(1.0, float(ref[1].abs().max())))
@@ -180,7 +168,7 @@ def test_fk_rows_equal_quaternion_composition(host, pose):
     order, parent = skel_arrays(edges, B)
     a_so3, a_loc = arr(so3), arr(local)
     qr, qd = np.empty((R, B, 4), np.float32), np.empty((R, B, 4), np.float32)
-    host.fk_host_forward(fp(a_so3), fp(a_loc), None, ip(order), ip(parent), R, B, 0, fp(qr), fp(qd))
+    host.fk_host_forward(dp(a_so3), dp(a_loc), None, dp(order), dp(parent), R, B, 0, dp(qr), dp(qd))
     qr_t, qd_t = torch.from_numpy(qr), torch.from_numpy(qd)
     t = 2 * O.quaternion_mul(qd_t, O.quaternion_conjugate(qr_t))[..., 1:]
     got = RO.quaternion_translation_to_se3(qr_t, t)

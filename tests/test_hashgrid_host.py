@@ -1,30 +1,17 @@
 """The multiresolution hash encoding's arithmetic (lab4d_amd/csrc/hashgrid_math.hpp, g++ build) against
 oracle/hashgrid_oracle.py (an independent vectorised restatement of the Instant-NGP paper; parity vs the reference is
 unpinned -- the reference has no hash grid) plus properties the definition implies.  CPU only."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
+import host_twin
 from oracle import hashgrid_oracle as HO
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def host():
-    out = os.path.join(ROOT, "tests", "host_harness", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "hashgrid_host.so")
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_harness", "hashgrid_host.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.hashgrid_host_forward.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-    lib.hashgrid_host_backward.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
-    return lib
+    return host_twin.load("hashgrid")
 
 
 def run_host(host, x, table, res, log2_T, g_out=None):

@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hashsdf_checks as HC  # noqa: E402
+import host_twin  # noqa: E402
 
 import lab4d_amd.hashsdf  # noqa: E402,F401  (the feature under test: its host layer must import without a GPU)
 
@@ -117,32 +118,24 @@ def test_zero_table_gives_loss_one_and_finite_gradients(host):
 
 def test_twin_runs_clean_under_the_sanitizers():
     """the stand-alone program over the special points of the rules, AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU"""
-    exe = HC.build_sanitized_main()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([host_twin.sanitized_main("hashsdf")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "hashsdf_host_main: ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
 
 
 def test_no_hashsdf_kernel_uses_scratch(tmp_path):
     """csrc/hashsdf.hip compiled for gfx950 as the build does: the code-object metadata of the three kernels (the forward and the adjoint
     once per F in 1, 2, 4, 8, and the reduce) reports no private segment and no spills."""
-    from lab4d_amd import _lib
-    src = os.path.join(_lib.CSRC, "hashsdf.hip")
-    subprocess.check_call([_lib.HIPCC] + _lib.CFLAGS + ["-save-temps=obj", "-c", src, "-o", str(tmp_path / "hashsdf.o")])
-    asm = [f for f in os.listdir(tmp_path) if f.endswith(".s") and "amdgcn" in f]
-    assert len(asm) == 1, asm
-    text = open(tmp_path / asm[0]).read()
-    names = re.findall(r"^\s+\.name:\s+(_ZN5lab4d\w+)$", text, flags=re.M)
+    kernels = host_twin.kernel_metadata("hashsdf.hip", tmp_path)
+    names = [k["name"] for k in kernels]
     assert len(names) == 9, names
     for kernel, n in (("k_hashsdf_fwd", 4), ("k_hashsdf_bwd", 4), ("k_hashsdf_reduce", 1)):
         assert sum(kernel in x for x in names) == n, (kernel, names)
     for key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
-        vals = re.findall(r"^\s+\.%s:\s+(\d+)$" % key, text, flags=re.M)
-        assert len(vals) == len(names) and set(vals) == {"0"}, (key, vals)
+        assert {k[key] for k in kernels} == {0}, (key, kernels)
     # three waves per SIMD: 512 / 3 registers rounded down to the allocation granule of 8 = 168.  The empty-asm pins of hashsdf_math.hpp hold
     # the allocation there; undone by a compiler, the kernels fall back to one wave per SIMD (256 VGPRs + AGPR copies) without spilling
-    vals = [int(v) for v in re.findall(r"^\s+\.vgpr_count:\s+(\d+)$", text, flags=re.M)]  # (the unified count: AGPRs included)
-    assert len(vals) == len(names) and max(vals) <= 168, vals
-    assert all(int(v) == 0 for v in re.findall(r"^\s+\.agpr_count:\s+(\d+)$", text, flags=re.M))
+    assert max(k["vgpr_count"] for k in kernels) <= 168, kernels  # (the unified count: AGPRs included)
+    assert all(k["agpr_count"] == 0 for k in kernels), kernels
 
 
 def test_host_layer_checks_its_arguments():

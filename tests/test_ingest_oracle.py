@@ -1,13 +1,12 @@
 """Batch ingestion, CPU side: oracle/ingest_oracle.py against the fixture the REAL `VidDataset` generated
 (tests/golden/ingest.pt), bit for bit; and the g++ build of the kernel's own arithmetic header (csrc/ingest_math.hpp) against both."""
-import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_twin
 from oracle import ingest_oracle as IO
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,16 +49,7 @@ def test_load_data_pair_stacking_and_pixel_index_arithmetic(gold):
 
 @pytest.fixture(scope="module")
 def host():
-    out = os.path.join(ROOT, "tests", "host_harness", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "ingest_host.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_harness", "ingest_host.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.ingest_host_bilinear.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    lib.ingest_host_double_to_half.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    lib.ingest_host_half_to_double.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    return lib
+    return host_twin.load("ingest")
 
 
 def test_half_conversions_of_the_kernel_header_are_exact(host):

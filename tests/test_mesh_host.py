@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_twin  # noqa: E402
 import mesh_checks as MC  # noqa: E402
 
 ROOT = MC.ROOT
@@ -169,18 +170,9 @@ def test_mesh_entry_points_validate_before_any_launch():
     """include/lab4d_mesh.h through ctypes, without a GPU: null volume, zero dimension, too large a grid -> LAB4D_EINVAL and a message."""
     from lab4d_amd import _lib
     _lib.build(verbose=False)
-    so = ctypes.CDLL(_lib.SO_PATH)
-    so.lab4d_last_error.restype = ctypes.c_char_p
-    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    so.lab4d_mesh_work_ints.restype = ctypes.c_int64
-    so.lab4d_mesh_work_ints.argtypes = [ci, ci, ci]
-    so.lab4d_mesh_component_work_ints.restype = ctypes.c_int64
-    so.lab4d_mesh_component_work_ints.argtypes = [ci, ci]
-    so.lab4d_mesh_count.argtypes = [vp, vp, ci, ci, ci, cf, vp, vp, vp]
-    so.lab4d_mesh_emit.argtypes = [vp, ci, ci, ci, cf, vp, vp, ci, ci, vp, vp, vp]
-    so.lab4d_mesh_largest_component.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, vp]
+    so = _lib.lib()  # (the signatures: from include/lab4d_mesh.h)
     buf = ctypes.create_string_buffer(64)
-    b = ctypes.cast(buf, vp)
+    b = ctypes.cast(buf, ctypes.c_void_p)
     assert so.lab4d_mesh_count(None, None, 4, 4, 4, 0.0, b, b, None) == -1 and b"null" in so.lab4d_last_error()
     assert so.lab4d_mesh_count(b, None, 4, 0, 4, 0.0, b, b, None) == -1 and b">= 1" in so.lab4d_last_error()
     assert so.lab4d_mesh_count(b, None, 1024, 1024, 1024, 0.0, b, b, None) == -1 and b"too large" in so.lab4d_last_error()
@@ -217,15 +209,8 @@ def test_mesh_object_has_the_fields_the_bound_updates_read():
 
 def test_no_mesh_kernel_uses_scratch(tmp_path):
     """csrc/mesh.hip compiled for gfx950 as the build does: every kernel's code-object metadata reports no private segment and no spills."""
-    import re
-    from lab4d_amd import _lib
-    src = os.path.join(_lib.CSRC, "mesh.hip")
-    subprocess.check_call([_lib.HIPCC] + _lib.CFLAGS + ["-save-temps=obj", "-c", src, "-o", str(tmp_path / "mesh.o")])
-    asm = [f for f in os.listdir(tmp_path) if f.endswith(".s") and "amdgcn" in f]
-    assert len(asm) == 1, asm
-    text = open(tmp_path / asm[0]).read()
-    names = re.findall(r"^\s+\.name:\s+(_ZN5lab4d\w+)$", text, flags=re.M)
-    assert len(names) >= 14 and all("k_mc_" in n or "k_cc_" in n for n in names), names
+    kernels = host_twin.kernel_metadata("mesh.hip", tmp_path)
+    names = [k["name"] for k in kernels]
+    assert len(names) >= 14 and all(n.startswith("_ZN5lab4d") and ("k_mc_" in n or "k_cc_" in n) for n in names), names
     for key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
-        vals = re.findall(r"^\s+\.%s:\s+(\d+)$" % key, text, flags=re.M)
-        assert len(vals) == len(names) and set(vals) == {"0"}, (key, vals)
+        assert {k[key] for k in kernels} == {0}, (key, kernels)

@@ -5,7 +5,6 @@ the kernels' distance, face and closest point bit for bit to this twin.  CPU onl
 import functools
 import itertools
 import os
-import re
 import subprocess
 import sys
 
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_twin  # noqa: E402
 import meshsdf_checks as SC  # noqa: E402
 
 import lab4d_amd.meshsdf  # noqa: E402,F401  (the feature under test: its host layer must import without a GPU)
@@ -207,24 +207,17 @@ def test_sliced_variant_is_bit_equal(host, name):
 
 def test_twin_runs_clean_under_the_sanitizers():
     """the stand-alone program over the edge cases of the rules, AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU"""
-    exe = SC.build_sanitized_main()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([host_twin.sanitized_main("meshsdf")], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "meshsdf_host_main: ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
 
 
 def test_no_meshsdf_kernel_uses_scratch(tmp_path):
     """csrc/meshsdf.hip compiled for gfx950 as the build does: both kernels' code-object metadata reports no private segment and no spills."""
-    from lab4d_amd import _lib
-    src = os.path.join(_lib.CSRC, "meshsdf.hip")
-    subprocess.check_call([_lib.HIPCC] + _lib.CFLAGS + ["-save-temps=obj", "-c", src, "-o", str(tmp_path / "meshsdf.o")])
-    asm = [f for f in os.listdir(tmp_path) if f.endswith(".s") and "amdgcn" in f]
-    assert len(asm) == 1, asm
-    text = open(tmp_path / asm[0]).read()
-    names = re.findall(r"^\s+\.name:\s+(_ZN5lab4d\w+)$", text, flags=re.M)
+    kernels = host_twin.kernel_metadata("meshsdf.hip", tmp_path)
+    names = [k["name"] for k in kernels]
     assert len(names) == 2 and any("k_mesh_sdf_partial" in n for n in names) and any("k_mesh_sdf_reduce" in n for n in names), names
     for key in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
-        vals = re.findall(r"^\s+\.%s:\s+(\d+)$" % key, text, flags=re.M)
-        assert len(vals) == len(names) and set(vals) == {"0"}, (key, vals)
+        assert {k[key] for k in kernels} == {0}, (key, kernels)
 
 
 def test_host_layer_checks_its_arguments():

@@ -2,27 +2,17 @@
 CPU with g++ and compared with torch.optim.AdamW / clip_grad_norm_ on CPU tensors.  CPU only; tests/test_gpu_zoptim.py runs
 the kernels."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_twin
 
 
 @pytest.fixture(scope="module")
 def host():
-    out = os.path.join(ROOT, "tests", "host_harness", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "optim_host.so")
-    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_harness", "optim_host.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.adamw_host_step.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_float] * 4 + \
-                                   [ctypes.c_int, ctypes.c_float]
-    return lib
+    return host_twin.load("optim")
 
 
 def test_adamw_rows_match_torch(host):
@@ -65,7 +55,6 @@ def test_flat_adamw_host_logic(host, monkeypatch):
     class FakeLib:
         @staticmethod
         def lab4d_grad_norm_clip(g, n, max_norm, work, norm, coef, stream):
-            host.grad_norm_clip_host.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
             return host.grad_norm_clip_host(g, n, max_norm, norm, coef)
 
         @staticmethod

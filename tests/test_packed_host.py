@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import host_twin  # noqa: E402
 import occgrid_checks as OC  # noqa: E402
 import packed_checks as PC  # noqa: E402
 
@@ -129,6 +130,5 @@ def test_composite_twin_zero_length_ray_between_long_ones():
 
 def test_twin_runs_clean_under_the_sanitizers():
     """the stand-alone program over the truncation cases and the rays without samples, AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU"""
-    exe = PC.build_sanitized_main()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([host_twin.sanitized_main("packed")], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "packed_host_main: ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])

@@ -3,7 +3,6 @@ BIT to the reference's own function (lab4d/utils/render_utils.py:187-233 restate
 searchsorted indices and samples, the u = 1 end point included.  That end point depends on the last ulp of the row normaliser
 torch.sum(weights + eps, -1), i.e. on the ORDER in which ATen's CPU kernel adds the row up (4 vector accumulators of 8 lanes, then lanes
 and tail sequentially); the header reproduces that order.  CPU only; tests/test_gpu_ops.py runs the same header on the device."""
-import ctypes
 import os
 import subprocess
 import sys
@@ -12,23 +11,13 @@ import numpy as np
 import pytest
 import torch
 
+import host_twin
 from oracle import lab4d_oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def host():
-    out = os.path.join(ROOT, "tests", "host_harness", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "sample_pdf_host.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "lab4d_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_harness", "sample_pdf_host.cpp"), "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.row_sum_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_float]
-    lib.row_sum_host.restype = ctypes.c_float
-    lib.sample_pdf_host.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float] + [ctypes.c_void_p] * 2
-    return lib
+    return host_twin.load("sample_pdf")
 
 
 def rows(seed, R, n):
@@ -54,7 +43,6 @@ def test_linspace_arithmetic(host):
     """The det=True queries: torch.linspace(0, 1, n) on the CPU is start + step * k for the first half and end - step * (n - 1 - k) -- evaluated with a
     FUSED multiply-add by ATen's vectorised kernel -- for the second; the header's formula gives the same floats for every n the renderer can
     use (n_depth // 2 for n_depth = 4 .. 512)."""
-    host.linspace01_host.argtypes = [ctypes.c_int, ctypes.c_void_p]
     for n in list(range(2, 260)) + [300, 512, 1000]:
         out = np.empty(n, np.float32)
         host.linspace01_host(n, out.ctypes.data)
