@@ -217,8 +217,10 @@ class _ProfiledLib:
             return fn
 
         def call(*a):
-            with timed(name[6:]):
-                return fn(*a)
+            with timed(name[6:]) as t:
+                rc = fn(*a)
+                t.on = t.on and rc == 0  # refused on the host: nothing was launched, nothing to time
+            return rc
         return call
 
 
@@ -385,10 +387,10 @@ class timed:
             self.s.record()
         return self
 
-    def __exit__(self, *a):
+    def __exit__(self, exc_type, *a):
         global _TIMED_DEPTH
         _TIMED_DEPTH -= 1
-        if self.on and PROF is not None:
+        if self.on and PROF is not None and exc_type is None:  # (a block that raised -- an entry point refused its arguments -- is no launch)
             self.e.record()
             PROF.setdefault(self.name, []).append((self.s, self.e, self.work))
         return False
