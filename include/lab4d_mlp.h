@@ -201,7 +201,10 @@ int lab4d_mlp_backward(const lab4d_mlp_bwd_args* a, void* stream);
 /* Weight / bias gradients of one layer: dW[o][k] = sum_s dz[o][s] * X[k][s], db[o] = sum_s dz[o][s],
  * X = [emb (ke rows) ; act_prev (kin rows)].  dW: (mout_pad, ke+kin) fp32 row-major, db: (mout_pad);
  * both are ACCUMULATED into (atomicAdd) -- zero-fill first.  pf_db: (M, mout_pad) per-frame bias
- * gradient or NULL (accumulated, zero-fill first).  When pf_db is given, db is NOT written: db = sum_m pf_db[m]. */
+ * gradient or NULL (accumulated, zero-fill first); it needs M > 0, spf > 0 and M * spf >= S.  When pf_db is given and the
+ * frames are 256-sample aligned (spf % 256 == 0) the row sums go to pf_db INSTEAD of db, which is not touched: db = sum_m
+ * pf_db[m].  Otherwise (a second pass fills pf_db) db receives the row sums as usual.  Either way sum_m pf_db[m] is the
+ * bias gradient. */
 int lab4d_mlp_wgrad(int net, int layer, int precision, int S, int S_pad, int ld, int spf, const void* dz, const void* emb,
                     const void* act_prev, float* dW, float* db, float* pf_db, int M, void* stream);
 /* The same contraction with the result accumulated (atomically) straight into a gradient buffer in the REFERENCE layout --

@@ -771,6 +771,8 @@ extern "C" int lab4d_mlp_wgrad_mapped(int net, int layer, int precision, int S, 
   // per-frame bias gradient folded into this kernel when frames are 256-sample aligned: chunks never straddle a
   // frame and the row sums of dz go straight to pf_db (saves a second pass over dz)
   const bool fold_pf = pf_db != nullptr && spf % 256 == 0 && M > 0 && (long)M * spf >= S;
+  // refused before anything is launched; k_rowsum_pf files sample s under frame s / spf, which has to be a row of the (M, mout_pad) table
+  LAB4D_REQUIRE(pf_db == nullptr || fold_pf || (M > 0 && spf > 0 && (long)M * spf >= S), "mlp_wgrad: pf_db needs M and spf, with M * spf >= S");
   int cpf = 0;
   if (fold_pf) {
     if (chunk > spf) chunk = spf;
@@ -813,7 +815,6 @@ extern "C" int lab4d_mlp_wgrad_mapped(int net, int layer, int precision, int S, 
 #undef WG
   if (int e = check_launch("mlp_wgrad")) return e;
   if (pf_db && !fold_pf) {
-    LAB4D_REQUIRE(M > 0 && spf > 0, "mlp_wgrad: pf_db needs M and spf");
     const int nseg = div_up(S, 4096);
     const long jobs2 = (long)L.mout_pad * nseg;
     if (precision == LAB4D_PREC_BF16)
