@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "hd_math.hpp"
 #include "lab4d_hip.h"
 
 namespace lab4d {
@@ -66,21 +67,20 @@ __device__ __forceinline__ float wave_rscan_incl(float v, int lane) {
   return v;
 }
 
-// A rounded fp32 product / sum that the optimiser cannot fuse into an fma.  HIP compiles with -ffp-contract=fast and the
-// backend contracts even __fmul_rn / __fadd_rn (found on the first hardware run of the hash grid, round 2), so wherever the
-// reference's arithmetic rounds a product before using it, the product is made opaque.
-__device__ __forceinline__ float mul_rn(float a, float b) {
-  float p = a * b;
-  asm volatile("" : "+v"(p));
-  return p;
-}
-__device__ __forceinline__ float add_rn(float a, float b) {
-  float p = a + b;
-  asm volatile("" : "+v"(p));
-  return p;
-}
+// A rounded fp32 product / sum that the optimiser cannot fuse into an fma (hd_math.hpp): wherever the reference's arithmetic rounds
+// a product before using it.
+using lab4d_rn::add_rn;
+using lab4d_rn::mul_rn;
 
 inline int div_up(long a, long b) { return (int)((a + b - 1) / b); }
 __device__ __forceinline__ int div_up_dev(int a, int b) { return (a + b - 1) / b; }
+
+// Blocks of a 1-D launch over n items, per_block items to a block, clamped to [1, cap]: the kernels behind it walk a grid-stride loop, so
+// cap bounds the grid and not the work.  Every call site passes its own cap (1024 .. 16384 across the kernels; they have not been
+// measured against one another).
+inline int grid_1d(long n, int per_block, int cap) {
+  const long g = (n + per_block - 1) / per_block;
+  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
+}
 
 }  // namespace lab4d

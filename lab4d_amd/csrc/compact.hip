@@ -123,15 +123,10 @@ __global__ void __launch_bounds__(256) k_frame_of(const int* __restrict__ idx, c
 }  // namespace lab4d
 using namespace lab4d;
 
-static int grid_for(long n) {
-  long g = (n + 255) / 256;
-  return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
 extern "C" int lab4d_valid_mask(const float* xyz, const float* xyz_t, const float* aabb, const float* t_aabb, long S, unsigned char* mask, void* stream) {
   LAB4D_REQUIRE(xyz && aabb && mask && (t_aabb == nullptr || xyz_t), "valid_mask: null pointer");
   if (S == 0) return LAB4D_OK;
-  hipLaunchKernelGGL(k_valid_mask, dim3(grid_for(S)), dim3(256), 0, (hipStream_t)stream, xyz, xyz_t, aabb, t_aabb, S, mask);
+  hipLaunchKernelGGL(k_valid_mask, dim3(grid_1d(S, 256, 8192)), dim3(256), 0, (hipStream_t)stream, xyz, xyz_t, aabb, t_aabb, S, mask);
   return check_launch("valid_mask");
 }
 
@@ -155,20 +150,20 @@ extern "C" int lab4d_compact(const unsigned char* mask, long S, int* idx, int* c
 extern "C" int lab4d_gather_rows(const float* src, const int* idx, const int* count, long n_rows, int C, float* dst, void* stream) {
   LAB4D_REQUIRE(src && idx && count && dst && C > 0, "gather_rows: bad arguments");
   if (n_rows == 0) return LAB4D_OK;
-  hipLaunchKernelGGL(k_gather_rows, dim3(grid_for(n_rows * C)), dim3(256), 0, (hipStream_t)stream, src, idx, count, n_rows, C, dst);
+  hipLaunchKernelGGL(k_gather_rows, dim3(grid_1d(n_rows * C, 256, 8192)), dim3(256), 0, (hipStream_t)stream, src, idx, count, n_rows, C, dst);
   return check_launch("gather_rows");
 }
 
 extern "C" int lab4d_scatter_rows(const float* src, const int* idx, const int* count, long n_rows, int C, float* dst, void* stream) {
   LAB4D_REQUIRE(src && idx && count && dst && C > 0, "scatter_rows: bad arguments");
   if (n_rows == 0) return LAB4D_OK;
-  hipLaunchKernelGGL(k_scatter_rows, dim3(grid_for(n_rows * C)), dim3(256), 0, (hipStream_t)stream, src, idx, count, n_rows, C, dst);
+  hipLaunchKernelGGL(k_scatter_rows, dim3(grid_1d(n_rows * C, 256, 8192)), dim3(256), 0, (hipStream_t)stream, src, idx, count, n_rows, C, dst);
   return check_launch("scatter_rows");
 }
 
 extern "C" int lab4d_frame_of(const int* idx, const int* count, long n_rows, int spf, int* frame, void* stream) {
   LAB4D_REQUIRE(idx && count && frame && spf > 0, "frame_of: bad arguments");
   if (n_rows == 0) return LAB4D_OK;
-  hipLaunchKernelGGL(k_frame_of, dim3(grid_for(n_rows)), dim3(256), 0, (hipStream_t)stream, idx, count, n_rows, spf, frame);
+  hipLaunchKernelGGL(k_frame_of, dim3(grid_1d(n_rows, 256, 8192)), dim3(256), 0, (hipStream_t)stream, idx, count, n_rows, spf, frame);
   return check_launch("frame_of");
 }

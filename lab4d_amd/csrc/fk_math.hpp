@@ -9,17 +9,11 @@
 // The reference runs this as a 25-iteration Python loop over (..,4,4) matrices with clone / index_put per joint (~150
 // launches forward, more in backward); here one thread owns one row and keeps the whole tree in its private arrays.
 //
-// The functions are plain C++ (LAB4D_HD = __host__ __device__ under hipcc, nothing otherwise) so that the CPU test-suite
-// can compile this very header with g++ and hold the arithmetic to the oracle without a GPU (tests/host_harness/): that
-// harness is test infrastructure, the product only ever launches the kernels of fk.hip.
+// The functions are plain C++ (LAB4D_HD of hd_math.hpp = __host__ __device__ under hipcc, nothing otherwise) so that the CPU
+// test-suite can compile this very header with g++ and hold the arithmetic to the oracle without a GPU (tests/host_harness/):
+// that harness is test infrastructure, the product only ever launches the kernels of fk.hip.
 #pragma once
-#include <math.h>
-
-#if defined(__HIPCC__)
-#define LAB4D_HD __host__ __device__ inline
-#else
-#define LAB4D_HD inline
-#endif
+#include "hd_math.hpp"
 
 namespace lab4d_fk {
 

@@ -133,7 +133,6 @@ __global__ void __launch_bounds__(256) k_volsdf_bwd(const float* __restrict__ sd
 }  // namespace lab4d
 using namespace lab4d;
 
-static int grid1(long n) { long g = (n + 255) / 256; return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g)); }
 
 extern "C" int lab4d_flow_cyc_forward(const float* xyz_next, const float* q, const float* t, const float* K, const float* hxy, const float* xyz_cyc,
                                       const float* xyz_t, long S, int spf, int D, float flow_thresh, float* flow, float* cyc, void* stream) {
@@ -141,7 +140,7 @@ extern "C" int lab4d_flow_cyc_forward(const float* xyz_next, const float* q, con
   LAB4D_REQUIRE((xyz_cyc == nullptr) == (cyc == nullptr) && (xyz_cyc == nullptr) == (xyz_t == nullptr), "flow_cyc_forward: cycle inputs / output go together");
   LAB4D_REQUIRE(spf > 0 && D > 0 && spf % D == 0, "flow_cyc_forward: samples per frame must be a multiple of samples per ray");
   if (S == 0) return LAB4D_OK;
-  hipLaunchKernelGGL(k_flow_cyc_fwd, dim3(grid1(S)), dim3(256), 0, (hipStream_t)stream, xyz_next, q, t, K, hxy, xyz_cyc, xyz_t, S, spf, D, flow_thresh, flow, cyc);
+  hipLaunchKernelGGL(k_flow_cyc_fwd, dim3(grid_1d(S, 256, 8192)), dim3(256), 0, (hipStream_t)stream, xyz_next, q, t, K, hxy, xyz_cyc, xyz_t, S, spf, D, flow_thresh, flow, cyc);
   return check_launch("flow_cyc_forward");
 }
 
@@ -165,7 +164,7 @@ extern "C" int lab4d_flow_cyc_backward(const float* xyz_next, const float* q, co
 extern "C" int lab4d_volsdf_forward(const float* sdf, const float* ibeta, long S, float* density, void* stream) {
   LAB4D_REQUIRE(sdf && ibeta && density, "volsdf_forward: null pointer");
   if (S == 0) return LAB4D_OK;
-  hipLaunchKernelGGL(k_volsdf_fwd, dim3(grid1(S)), dim3(256), 0, (hipStream_t)stream, sdf, ibeta, S, density);
+  hipLaunchKernelGGL(k_volsdf_fwd, dim3(grid_1d(S, 256, 8192)), dim3(256), 0, (hipStream_t)stream, sdf, ibeta, S, density);
   return check_launch("volsdf_forward");
 }
 
@@ -175,6 +174,6 @@ extern "C" int lab4d_volsdf_backward(const float* sdf, const float* ibeta, const
   if (g_ibeta)
     if (int e = zero_async(g_ibeta, sizeof(float), st)) return e;
   if (S == 0) return LAB4D_OK;
-  hipLaunchKernelGGL(k_volsdf_bwd, dim3(grid1(S) > 1024 ? 1024 : grid1(S)), dim3(256), 0, st, sdf, ibeta, g_density, S, g_sdf, g_ibeta);
+  hipLaunchKernelGGL(k_volsdf_bwd, dim3(grid_1d(S, 256, 1024)), dim3(256), 0, st, sdf, ibeta, g_density, S, g_sdf, g_ibeta);
   return check_launch("volsdf_backward");
 }

@@ -144,9 +144,8 @@ extern "C" int lab4d_hashgrid_forward(const float* x, const float* table, const 
                                       void* stream) {
   HASH_CHECKS("hashgrid_forward");
   LAB4D_REQUIRE(out, "hashgrid_forward: null output");
-  long g = (S + 255L) / 256;
-  if (g > 16384) g = 16384;
-  hipLaunchKernelGGL(k_hashgrid_fwd<false>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, x, table, res, S, L, log2_T, F, out);
+  const int g = grid_1d(S, 256, 16384);
+  hipLaunchKernelGGL(k_hashgrid_fwd<false>, dim3(g), dim3(256), 0, (hipStream_t)stream, x, table, res, S, L, log2_T, F, out);
   return check_launch("hashgrid_forward");
 }
 
@@ -154,15 +153,13 @@ extern "C" int lab4d_hashgrid_forward_inside(const float* x, const float* table,
                                              void* stream) {
   HASH_CHECKS("hashgrid_forward_inside");
   LAB4D_REQUIRE(out, "hashgrid_forward_inside: null output");
-  long g = (S + 255L) / 256;
-  if (g > 16384) g = 16384;
+  const int g = grid_1d(S, 256, 16384);
   static const int lm = getenv("LAB4D_HASH_LEVEL_MAJOR") ? atoi(getenv("LAB4D_HASH_LEVEL_MAJOR")) : 1;  // 0: the sample-major kernel (A/B measurements)
   if (lm && S >= 65536) {
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(k_hashgrid_fwd_lm<true>, dim3((int)g, L), dim3(256), 0, (hipStream_t)stream, x, table, res, S, L, log2_T, F, out);
+    hipLaunchKernelGGL(k_hashgrid_fwd_lm<true>, dim3(grid_1d(S, 256, 4096), L), dim3(256), 0, (hipStream_t)stream, x, table, res, S, L, log2_T, F, out);
     return check_launch("hashgrid_forward_inside");
   }
-  hipLaunchKernelGGL(k_hashgrid_fwd<true>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, x, table, res, S, L, log2_T, F, out);
+  hipLaunchKernelGGL(k_hashgrid_fwd<true>, dim3(g), dim3(256), 0, (hipStream_t)stream, x, table, res, S, L, log2_T, F, out);
   return check_launch("hashgrid_forward_inside");
 }
 
@@ -170,18 +167,16 @@ extern "C" int lab4d_hashgrid_backward(const float* x, const float* table, const
                                        float* g_table, float* g_x, void* stream) {
   HASH_CHECKS("hashgrid_backward");
   LAB4D_REQUIRE(g_out && (g_table || g_x), "hashgrid_backward: null pointer");
-  long g = (S + 255L) / 256;
-  if (g > 16384) g = 16384;
-  hipLaunchKernelGGL(k_hashgrid_bwd, dim3((int)g), dim3(256), 0, (hipStream_t)stream, x, table, res, g_out, S, L, log2_T, F, g_table, g_x);
+  const int g = grid_1d(S, 256, 16384);
+  hipLaunchKernelGGL(k_hashgrid_bwd, dim3(g), dim3(256), 0, (hipStream_t)stream, x, table, res, g_out, S, L, log2_T, F, g_table, g_x);
   return check_launch("hashgrid_backward");
 }
 
 extern "C" int lab4d_hashgrid_absmax(const float* g_out, long n, uint32_t* absmax_bits, void* stream) {
   LAB4D_REQUIRE(g_out && absmax_bits && n >= 0, "hashgrid_absmax: bad arguments");
   if (n == 0) return LAB4D_OK;
-  long g = (n + 255L) / 256;
-  if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(k_hash_absmax, dim3((int)g), dim3(256), 0, (hipStream_t)stream, g_out, n, absmax_bits);
+  const int g = grid_1d(n, 256, 4096);
+  hipLaunchKernelGGL(k_hash_absmax, dim3(g), dim3(256), 0, (hipStream_t)stream, g_out, n, absmax_bits);
   return check_launch("hashgrid_absmax");
 }
 
@@ -191,9 +186,8 @@ extern "C" int lab4d_hashgrid_backward_f16(const float* x, const float* table, c
   HASH_CHECKS("hashgrid_backward_f16");
   LAB4D_REQUIRE(g_out && g_table && g16 && absmax_bits, "hashgrid_backward_f16: null pointer");
   LAB4D_REQUIRE(first_f16_level >= 0 && first_f16_level <= L, "hashgrid_backward_f16: first_f16_level %d outside 0..%d", first_f16_level, L);
-  long g = (S + 255L) / 256;
-  if (g > 16384) g = 16384;
-  hipLaunchKernelGGL(k_hashgrid_bwd_h2, dim3((int)g), dim3(256), 0, (hipStream_t)stream, x, table, res, g_out, S, L, log2_T, first_f16_level, g_table, g16,
+  const int g = grid_1d(S, 256, 16384);
+  hipLaunchKernelGGL(k_hashgrid_bwd_h2, dim3(g), dim3(256), 0, (hipStream_t)stream, x, table, res, g_out, S, L, log2_T, first_f16_level, g_table, g16,
                      absmax_bits, g_x);
   return check_launch("hashgrid_backward_f16");
 }
@@ -203,8 +197,7 @@ extern "C" int lab4d_hashgrid_flush_f16(uint32_t* g16, const uint32_t* absmax_bi
   LAB4D_REQUIRE(L > 0 && L <= 32 && log2_T >= 4 && log2_T <= 24 && first_f16_level >= 0 && first_f16_level <= L, "hashgrid_flush_f16: bad sizes");
   if (first_f16_level == L) return LAB4D_OK;
   const long T = 1L << log2_T, w0 = (long)first_f16_level * T, n = (long)L * T;
-  long g = (n - w0 + 255L) / 256;
-  if (g > 8192) g = 8192;
-  hipLaunchKernelGGL(k_hash_flush_h2, dim3((int)g), dim3(256), 0, (hipStream_t)stream, g16, absmax_bits, w0, n, g_table);
+  const int g = grid_1d(n - w0, 256, 8192);
+  hipLaunchKernelGGL(k_hash_flush_h2, dim3(g), dim3(256), 0, (hipStream_t)stream, g16, absmax_bits, w0, n, g_table);
   return check_launch("hashgrid_flush_f16");
 }

@@ -5,34 +5,19 @@
 //   x in [0,1]^3 is scaled by res, the 8 surrounding vertices are looked up -- 1:1 when (res+1)^3 <= T, otherwise through the
 //   spatial hash  (ix * 1) ^ (iy * 2654435761) ^ (iz * 805459861)  mod T  (paper eq. 4) -- and blended tri-linearly;
 //   F features per level, output (L * F) level-major.  Table layout (L, T, F) fp32.
-// Plain C++ (LAB4D_HD convention of fk_math.hpp): the CPU suite builds this header with g++ and holds it to
+// Plain C++ (LAB4D_HD convention of hd_math.hpp): the CPU suite builds this header with g++ and holds it to
 // oracle/hashgrid_oracle.py; the kernels of hashgrid.hip call the same functions.
 #pragma once
-#include <math.h>
-#include <stdint.h>
+#include "hd_math.hpp"
 
-#if defined(__HIPCC__)
-#define LAB4D_HD __host__ __device__ inline
-#else
-#define LAB4D_HD inline
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 #define LAB4D_ATOMIC_ADD(ptr, v) atomicAdd((ptr), (v))
-// x * res must be ROUNDED before the cell origin is subtracted: contracted into fma(x, res, -floor) the fractional position
-// differs from the definition by up to ulp(x * res) = 1.2e-4 at res = 2048 (first MI355X run of the large case: 2e-5 off)
-// (__fmul_rn alone is still fused by the backend under HIP's default -ffp-contract=fast: the product is made opaque instead)
-LAB4D_HD float lab4d_mul_rn(float a, float b) {
-    float p = a * b;
-    asm volatile("" : "+v"(p));
-    return p;
-}
-#define LAB4D_MUL_RN(a, b) lab4d_mul_rn((a), (b))
 #else
 #define LAB4D_ATOMIC_ADD(ptr, v) (*(ptr) += (v))
-#define LAB4D_MUL_RN(a, b) ((a) * (b))
 #endif
 
 namespace lab4d_hash {
+using lab4d_rn::mul_rn;
 
 constexpr int MAXF = 8;
 
@@ -46,7 +31,9 @@ LAB4D_HD uint32_t vertex_index(uint32_t ix, uint32_t iy, uint32_t iz, int res, i
 LAB4D_HD void cell_of(const float* x, int res, uint32_t* i0, float* w) {
     for (int a = 0; a < 3; ++a) {
         const float xc = fminf(fmaxf(x[a], 0.f), 1.f);
-        const float p = LAB4D_MUL_RN(xc, (float)res);
+        // x * res must be ROUNDED before the cell origin is subtracted: contracted into fma(x, res, -floor) the fractional position
+        // differs from the definition by up to ulp(x * res) = 1.2e-4 at res = 2048 (first MI355X run of the large case: 2e-5 off)
+        const float p = mul_rn(xc, (float)res);
         float f = floorf(p);
         if (f > (float)(res - 1)) f = (float)(res - 1);
         i0[a] = (uint32_t)f;

@@ -32,15 +32,11 @@
 // table entry and every corner weight stays live (8 L F + 5 * 8 L values; 256 VGPRs, as many AGPR copies, one wave per SIMD, spills at
 // F = 1).  A level's results are therefore pinned where the level ends.  (2) The table is walked twice per sample (enc, then grad01 or
 // the table adjoint) with the dense layer in between; the second walk must RECOMPUTE cells, weights and addresses instead of carrying
-// them across the dense layer, so the point is made opaque between the walks.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define LAB4D_PIN(v) asm volatile("" : "+v"(v))
-#else
-#define LAB4D_PIN(v) ((void)0)
-#endif
-#define LAB4D_OPAQUE3(y) do { LAB4D_PIN((y)[0]); LAB4D_PIN((y)[1]); LAB4D_PIN((y)[2]); } while (0)
+// them across the dense layer, so the point is made opaque between the walks.  Both are lab4d_rn::pin (hd_math.hpp; nothing on the host).
+#define LAB4D_OPAQUE3(y) do { lab4d_rn::pin((y)[0]); lab4d_rn::pin((y)[1]); lab4d_rn::pin((y)[2]); } while (0)
 
 namespace lab4d_hsdf {
+using lab4d_rn::pin;
 
 constexpr int kEnc = 32;                              // L * F, the width the geometry net is instantiated for
 constexpr int kHid = 64;
@@ -99,10 +95,10 @@ LAB4D_HD void gather_enc(const float* x, const float* table, const int* res, int
     }
 #pragma unroll
     for (int f = 0; f < F; ++f) {
-      LAB4D_PIN(a[f]);
+      pin(a[f]);
       enc[l * F + f] = a[f];
       if (e) {
-        LAB4D_PIN(b[f]);
+        pin(b[f]);
         e[l * F + f] = b[f];
       }
     }
@@ -157,7 +153,7 @@ LAB4D_HD void gather_grad(const float* x, const float* table, const int* res, in
     }
     for (int a = 0; a < 3; ++a) {
       grad01[a] += acc[a] * (float)r;
-      LAB4D_PIN(grad01[a]);
+      pin(grad01[a]);
     }
   }
 }

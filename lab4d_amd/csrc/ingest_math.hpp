@@ -3,31 +3,12 @@
 // without a GPU.  Everything here is bit-exact by construction: half <-> double conversions are exact / round-to-nearest-even,
 // and the bilinear interpolation repeats numpy's fp64 operation order (utils/numpy_utils.py:106-121).
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define LAB4D_HD __host__ __device__ __forceinline__
-#else
-#define LAB4D_HD inline
-#endif
+#include "hd_math.hpp"
 
 namespace lab4d_ingest {
-
-// a rounded fp64 product / sum the optimiser cannot contract into an fma (see common.hpp: mul_rn)
-LAB4D_HD double dmul(double a, double b) {
-  double p = a * b;
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(p));
-#endif
-  return p;
-}
-LAB4D_HD double dadd(double a, double b) {
-  double p = a + b;
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(p));
-#endif
-  return p;
-}
+// a rounded fp64 product / sum the optimiser cannot contract into an fma (see hd_math.hpp)
+using lab4d_rn::dadd;
+using lab4d_rn::dmul;
 
 LAB4D_HD double bits_to_double(uint64_t u) {
   union { uint64_t u; double d; } c;

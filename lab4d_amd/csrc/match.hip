@@ -24,12 +24,8 @@ __device__ __forceinline__ float dot16(const float (&f)[MC], const float4* row) 
 
 // score = (f . fc) * scale as a ROUNDED product: contracted into fma(dot, scale, -max) the subtraction would see the unrounded product in one
 // pass and the rounded one in the other (the row maximum would not be the maximum of the scores it is subtracted from)
-// (__fmul_rn alone is still fused by the backend under -ffp-contract=fast, see hashgrid_math.hpp: the product is made opaque instead)
-__device__ __forceinline__ float score(float d, float scale) {
-  float p = d * scale;
-  asm volatile("" : "+v"(p));
-  return p;
-}
+// (mul_rn: hd_math.hpp)
+__device__ __forceinline__ float score(float d, float scale) { return mul_rn(d, scale); }
 
 // out[r] = sum_i softmax_i(scale * f_r . fc_i) xc_i ; stats[r] = (max_i score, sum_i exp(score - max)).  One thread per ray; the candidates pass
 // through LDS in tiles of KT, twice: the row maximum first (the reference's softmax subtracts it before exponentiating), then the sums.

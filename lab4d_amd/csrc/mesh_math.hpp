@@ -1,6 +1,6 @@
 // Per-cell / per-edge arithmetic of the iso-surface extractor (csrc/mesh.hip; contract: include/lab4d_mesh.h) -- what the reference does
 // with skimage.measure.marching_cubes in geom_utils.marching_cubes (lab4d/utils/geom_utils.py:442-503).
-// Plain C++ behind LAB4D_HD (see fk_math.hpp): the kernels run it one thread per grid point, tests/host_harness/mesh_host.cpp compiles
+// Plain C++ behind LAB4D_HD (see hd_math.hpp): the kernels run it one thread per grid point, tests/host_harness/mesh_host.cpp compiles
 // it with g++ (-ffp-contract=off) as a serial loop over the same functions and the same table (mc_tables.hpp), so that the CPU test-suite
 // can pin the mesh by its properties and the GPU suite can hold the kernels bit for bit to the CPU twin.
 //
@@ -12,32 +12,16 @@
 //     p[axis] + (level - a) / (b - a); a != b is guaranteed by the crossing.  World position = origin + step * index position, per axis,
 //     product and sum rounded separately (no fused multiply-add on either side).
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
+#include "hd_math.hpp"
 #include "mc_tables.hpp"
 
-#if defined(__HIPCC__)
-#define LAB4D_HD __host__ __device__ inline
-#else
-#define LAB4D_HD inline
-#endif
-
 namespace lab4d_mc {
-
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ float add_rn(float a, float b) { float p = a + b; asm volatile("" : "+v"(p)); return p; }
-__device__ __forceinline__ float mul_rn(float a, float b) { float p = a * b; asm volatile("" : "+v"(p)); return p; }
-__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
-#else
-inline float add_rn(float a, float b) { volatile float p = a + b; return p; }
-inline float mul_rn(float a, float b) { volatile float p = a * b; return p; }
-inline float div_rn(float a, float b) { volatile float p = a / b; return p; }
-#endif
+using lab4d_rn::add_rn;
+using lab4d_rn::div_rn;
+using lab4d_rn::finite_f;
+using lab4d_rn::mul_rn;
 
 LAB4D_HD bool inside(float v, float level) { return v < level; }
-
-LAB4D_HD bool finite_f(float v) { return fabsf(v) <= 3.402823466e+38f; }  // false for inf and NaN
 
 // corner c of the cell whose corner 0 has linear index 0 in a (Gx, Gy, Gz) volume, Gz fastest
 LAB4D_HD long corner_offset(int c, int Gy, int Gz) { return (long)((c >> 0) & 1) * Gy * Gz + (long)((c >> 1) & 1) * Gz + ((c >> 2) & 1); }

@@ -1,7 +1,7 @@
 // Signed distance from points to a triangle mesh (csrc/meshsdf.hip; contract: include/lab4d_meshsdf.h): brute force, every point against
 // every face.  The device counterpart of the pysdf query behind NeRF.get_init_sdf_fn (nnutils/nerf.py:217-230); pysdf's own arithmetic
 // cannot be run where this project is built, so the rules below are this repository's own and parity with pysdf is unpinned.
-// Plain C++ behind LAB4D_HD (see fk_math.hpp): the kernels run these functions one lane per point, tests/host_harness/meshsdf_host.cpp
+// Plain C++ behind LAB4D_HD (see hd_math.hpp): the kernels run these functions one lane per point, tests/host_harness/meshsdf_host.cpp
 // compiles them with g++ (-ffp-contract=off) as serial loops, and the GPU suite holds the kernels' distance, face and closest point bit
 // for bit to that twin.
 //
@@ -9,7 +9,7 @@
 //           length of (b - a) x (c - a) is finite and > 0.  An invalid triangle is skipped, for the distance and for the sign.
 // DISTANCE  the closest point q of the triangle by region classification (vertex a, vertex b, edge ab, vertex c, edge ac, edge bc, face:
 //           Ericson, Real-Time Collision Detection, 5.1.5, in that order), d2 = |p - q|^2, d = sqrt(d2) correctly rounded.  Every product
-//           that feeds a sum or a comparison is rounded on its own (mul_rn: opaque to the optimiser on the device); the quotients are the
+//           that feeds a sum or a comparison is rounded on its own (mul_rn, see hd_math.hpp, as for sqrt_rn); the quotients are the
 //           correctly rounded division on both sides.  Over the faces the smallest d2 wins; a d2 that is not < +inf (overflow) never
 //           wins.  TIES go to the lowest face index: a strict < while walking the faces in ascending order, and a strict < in ascending
 //           slice order when partial results are combined.  d2, q and the winning face are therefore a pure function of the inputs,
@@ -25,32 +25,17 @@
 //           sdf = +inf, face = -1, closest = the point.
 // SLICES    slice s of n covers the faces [s * F / n, (s + 1) * F / n) (integer division in 64 bits); it may be empty.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define LAB4D_HD __host__ __device__ inline
-#else
-#define LAB4D_HD inline
-#endif
+#include "hd_math.hpp"
 
 namespace lab4d_msdf {
+using lab4d_rn::div_rn;
+using lab4d_rn::finite_f;
+using lab4d_rn::inf_f;
+using lab4d_rn::mul_rn;
+using lab4d_rn::nan_f;
+using lab4d_rn::sqrt_rn;
 
 constexpr int kWorkWords = 6;  // per (slice, point): d2, face, closest xyz, winding sum
-
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ float mul_rn(float a, float b) { float p = a * b; asm volatile("" : "+v"(p)); return p; }
-__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
-#else
-inline float mul_rn(float a, float b) { volatile float p = a * b; return p; }
-inline float div_rn(float a, float b) { volatile float p = a / b; return p; }
-#endif
-
-// correctly rounded on both sides: the double root of a float, rounded once more, is the float root (53 >= 2 * 24 + 2 bits), as in packed_math.hpp
-LAB4D_HD float sqrt_rn(float a) { return (float)sqrt((double)a); }
-LAB4D_HD bool finite_f(float v) { return fabsf(v) <= 3.402823466e+38f; }  // false for inf and NaN
-LAB4D_HD float inf_f() { return __builtin_huge_valf(); }
-LAB4D_HD float nan_f() { return __builtin_nanf(""); }
 
 LAB4D_HD long slice_lo(int s, int n_faces, int n_slices) { return (long)s * n_faces / n_slices; }
 

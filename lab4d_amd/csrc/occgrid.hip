@@ -57,11 +57,6 @@ __global__ void __launch_bounds__(256) k_occgrid_ray_span(const float* __restric
 }  // namespace lab4d
 using namespace lab4d;
 
-static int occ_grid_for(long n) {
-  long g = (n + 255) / 256;
-  return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
 #define LAB4D_OCC_REQUIRE_G(what) \
   LAB4D_REQUIRE(G >= lab4d_occ::kMinG && G <= lab4d_occ::kMaxG, what ": G = %d outside [%d, %d]", G, lab4d_occ::kMinG, lab4d_occ::kMaxG)
 
@@ -84,7 +79,7 @@ extern "C" int lab4d_occgrid_mask(const float* xyz, const float* aabb, const uin
   LAB4D_OCC_REQUIRE_G("occgrid_mask");
   if (S == 0) return LAB4D_OK;
   LAB4D_REQUIRE(xyz && aabb && bits && mask, "occgrid_mask: null pointer");
-  hipLaunchKernelGGL(k_occgrid_mask, dim3(occ_grid_for(S)), dim3(256), 0, (hipStream_t)stream, xyz, aabb, bits, G, S, mask);
+  hipLaunchKernelGGL(k_occgrid_mask, dim3(grid_1d(S, 256, 8192)), dim3(256), 0, (hipStream_t)stream, xyz, aabb, bits, G, S, mask);
   return check_launch("occgrid_mask");
 }
 
@@ -94,6 +89,6 @@ extern "C" int lab4d_occgrid_ray_span(const float* origin, const float* dir, con
   LAB4D_OCC_REQUIRE_G("occgrid_ray_span");
   if (R == 0) return LAB4D_OK;
   LAB4D_REQUIRE(origin && dir && t_range && aabb && bits && t_span && hit, "occgrid_ray_span: null pointer");
-  hipLaunchKernelGGL(k_occgrid_ray_span, dim3(occ_grid_for(R)), dim3(256), 0, (hipStream_t)stream, origin, dir, t_range, aabb, bits, G, R, t_span, hit);
+  hipLaunchKernelGGL(k_occgrid_ray_span, dim3(grid_1d(R, 256, 8192)), dim3(256), 0, (hipStream_t)stream, origin, dir, t_range, aabb, bits, G, R, t_span, hit);
   return check_launch("occgrid_ray_span");
 }

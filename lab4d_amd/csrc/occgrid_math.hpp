@@ -2,10 +2,10 @@
 // field's box, refreshed from the field's own density, consulted per sample (skip empty cells) and per ray (march only between the first
 // and the last occupied cell) -- Mueller et al. 2022, section 5.4 / appendix E.  The reference has no counterpart (nnutils/nerf.py:98 is
 // a TODO), so the rules below are this repository's own.
-// Plain C++ behind LAB4D_HD (see fk_math.hpp): the kernels run these functions one lane per cell / sample / ray,
+// Plain C++ behind LAB4D_HD (see hd_math.hpp): the kernels run these functions one lane per cell / sample / ray,
 // tests/host_harness/occgrid_host.cpp compiles them with g++ (-ffp-contract=off) as serial loops, and the GPU suite holds the kernels
-// bit for bit to that twin.  Every product that feeds a sum or a comparison is rounded on its own (mul_rn / add_rn: opaque to the
-// optimiser on the device, see common.hpp); 1 / d is the correctly rounded division on both sides.
+// bit for bit to that twin.  Every product that feeds a sum or a comparison is rounded on its own (mul_rn / add_rn, see hd_math.hpp);
+// 1 / d is the correctly rounded division on both sides.
 //
 // GRID   G cells per axis over aabb = {lo, hi}, 2 <= G <= 256.  x01 = (x - lo) / (hi - lo) per axis (the arithmetic of
 //        hashfield.forward).  A point has a cell iff 0 <= x01 <= 1 on every axis (NaN: no cell; an empty box hi <= lo: no point has one);
@@ -30,30 +30,15 @@
 //        occupied cell was visited; hit == 0: t_first = t_last = t0.  Every visited cell counts, also one crossed in zero length, so the
 //        span errs on the wide side.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define LAB4D_HD __host__ __device__ inline
-#else
-#define LAB4D_HD inline
-#endif
+#include "hd_math.hpp"
 
 namespace lab4d_occ {
+using lab4d_rn::add_rn;
+using lab4d_rn::div_rn;
+using lab4d_rn::finite_f;
+using lab4d_rn::mul_rn;
 
 constexpr int kMinG = 2, kMaxG = 256;
-
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ float add_rn(float a, float b) { float p = a + b; asm volatile("" : "+v"(p)); return p; }
-__device__ __forceinline__ float mul_rn(float a, float b) { float p = a * b; asm volatile("" : "+v"(p)); return p; }
-__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
-#else
-inline float add_rn(float a, float b) { volatile float p = a + b; return p; }
-inline float mul_rn(float a, float b) { volatile float p = a * b; return p; }
-inline float div_rn(float a, float b) { volatile float p = a / b; return p; }
-#endif
-
-LAB4D_HD bool finite_f(float v) { return fabsf(v) <= 3.402823466e+38f; }  // false for inf and NaN
 
 LAB4D_HD long n_cells(int G) { return (long)G * G * G; }
 LAB4D_HD long n_words(int G) { return (n_cells(G) + 31) >> 5; }

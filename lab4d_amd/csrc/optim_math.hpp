@@ -1,16 +1,10 @@
 // AdamW update of one element, written the way torch.optim.AdamW's single-tensor path orders it (torch/optim/adamw.py
 // _single_tensor_adamw: decay, lerp of the first moment, mul/addcmul of the second, bias corrections, addcdiv), which is
 // the optimizer the reference builds (lab4d/engine/trainer.py:185-190: betas (0.9, 0.999), weight_decay 1e-4, one group per
-// parameter with its own OneCycleLR learning rate).  Plain C++ (see fk_math.hpp for the LAB4D_HD convention): the CPU
+// parameter with its own OneCycleLR learning rate).  Plain C++ (see hd_math.hpp for the LAB4D_HD convention): the CPU
 // test-suite compiles this header with g++ and checks it against torch.optim.AdamW.
 #pragma once
-#include <math.h>
-
-#if defined(__HIPCC__)
-#define LAB4D_HD __host__ __device__ inline
-#else
-#define LAB4D_HD inline
-#endif
+#include "hd_math.hpp"
 
 namespace lab4d_optim {
 

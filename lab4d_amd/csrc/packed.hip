@@ -252,15 +252,10 @@ __global__ void __launch_bounds__(256) k_packed_composite_bwd(const float* __res
 }  // namespace lab4d
 using namespace lab4d;
 
-static int packed_grid_for(long n, int per_block) {
-  long g = (n + per_block - 1) / per_block;
-  return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g));
-}
-
 static int check_march(const char* what, int G, long R, float dt, int k_max) {
   LAB4D_REQUIRE(R >= 0, "%s: R < 0", what);
   LAB4D_REQUIRE(G >= lab4d_occ::kMinG && G <= lab4d_occ::kMaxG, "%s: G = %d outside [%d, %d]", what, G, lab4d_occ::kMinG, lab4d_occ::kMaxG);
-  LAB4D_REQUIRE(dt > 0.f && dt <= 3.402823466e+38f, "%s: dt = %g must be finite and > 0", what, (double)dt);
+  LAB4D_REQUIRE(dt > 0.f && lab4d_occ::finite_f(dt), "%s: dt = %g must be finite and > 0", what, (double)dt);
   LAB4D_REQUIRE(k_max >= 1, "%s: k_max = %d must be >= 1", what, k_max);
   LAB4D_REQUIRE(R * (long)k_max < (1L << 31), "%s: R * k_max = %ld * %d does not fit 31 bits", what, R, k_max);
   return LAB4D_OK;
@@ -271,7 +266,7 @@ extern "C" int lab4d_packed_march_count(const float* origin, const float* dir, c
   if (int e = check_march("packed_march_count", G, R, dt, k_max)) return e;
   if (R == 0) return LAB4D_OK;
   LAB4D_REQUIRE(origin && dir && t_range && aabb && bits && ray_count, "packed_march_count: null pointer");
-  hipLaunchKernelGGL(k_packed_march_count, dim3(packed_grid_for(R, 256)), dim3(256), 0, (hipStream_t)stream, origin, dir, t_range, aabb, bits, G, R, dt, k_max,
+  hipLaunchKernelGGL(k_packed_march_count, dim3(grid_1d(R, 256, 16384)), dim3(256), 0, (hipStream_t)stream, origin, dir, t_range, aabb, bits, G, R, dt, k_max,
                      ray_count);
   return check_launch("packed_march_count");
 }
@@ -285,11 +280,11 @@ extern "C" int lab4d_packed_march_write(const float* origin, const float* dir, c
   LAB4D_REQUIRE(R == 0 || (origin && dir && t_range && bits && ray_start && ray_count_out), "packed_march_write: null pointer");
   LAB4D_REQUIRE(cap == 0 || (t && deltas && xyz && dirs && ray_idx), "packed_march_write: null packed buffer");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_packed_march_write, dim3(packed_grid_for(R, 256)), dim3(256), 0, st, origin, dir, t_range, aabb, bits, G, R, dt, k_max, ray_start, cap, t,
+  hipLaunchKernelGGL(k_packed_march_write, dim3(grid_1d(R, 256, 16384)), dim3(256), 0, st, origin, dir, t_range, aabb, bits, G, R, dt, k_max, ray_start, cap, t,
                      deltas, xyz, dirs, ray_idx, ray_count_out, total, overflow);
   if (int e = check_launch("packed_march_write")) return e;
   if (cap == 0) return LAB4D_OK;
-  hipLaunchKernelGGL(k_packed_park, dim3(packed_grid_for(cap, 256)), dim3(256), 0, st, aabb, total, cap, t, deltas, xyz, dirs, ray_idx);
+  hipLaunchKernelGGL(k_packed_park, dim3(grid_1d(cap, 256, 16384)), dim3(256), 0, st, aabb, total, cap, t, deltas, xyz, dirs, ray_idx);
   return check_launch("packed_march_write (park)");
 }
 
@@ -315,7 +310,7 @@ extern "C" int lab4d_packed_composite_forward(const float* density, const float*
   LAB4D_REQUIRE(ray_start && ray_count, "packed_composite_forward: null ray_start / ray_count");
   LAB4D_REQUIRE(P == 0 || (density && deltas), "packed_composite_forward: null density / deltas");
   LAB4D_REQUIRE(sumC == 0 || out, "packed_composite_forward: out is null");
-  hipLaunchKernelGGL(k_packed_composite_fwd, dim3(packed_grid_for(R, 4)), dim3(256), 0, (hipStream_t)stream, density, deltas, *fl, ray_start, ray_count, R, P, sumC,
+  hipLaunchKernelGGL(k_packed_composite_fwd, dim3(grid_1d(R, 4, 16384)), dim3(256), 0, (hipStream_t)stream, density, deltas, *fl, ray_start, ray_count, R, P, sumC,
                      weights, transmit, mask, out);
   return check_launch("packed_composite_forward");
 }
@@ -329,7 +324,7 @@ extern "C" int lab4d_packed_composite_backward(const float* density, const float
   LAB4D_REQUIRE(g_fields && g_fields->n_fields == fl->n_fields, "packed_composite_backward: g_fields does not match the field list");
   if (R == 0 || P == 0) return LAB4D_OK;
   LAB4D_REQUIRE(ray_start && ray_count && density && deltas, "packed_composite_backward: null pointer");
-  hipLaunchKernelGGL(k_packed_composite_bwd, dim3(packed_grid_for(R, 4)), dim3(256), 0, (hipStream_t)stream, density, deltas, *fl, ray_start, ray_count, R, P, sumC,
+  hipLaunchKernelGGL(k_packed_composite_bwd, dim3(grid_1d(R, 4, 16384)), dim3(256), 0, (hipStream_t)stream, density, deltas, *fl, ray_start, ray_count, R, P, sumC,
                      g_mask, g_out, g_density, g_deltas, *g_fields);
   return check_launch("packed_composite_backward");
 }

@@ -30,10 +30,7 @@
 
 namespace lab4d_packed {
 namespace occ = lab4d_occ;
-
-// The correctly rounded fp32 square root on both sides: through the IEEE double root (53 >= 2 * 24 + 2 bits: rounding it to fp32 is the
-// correctly rounded result), which does not depend on how a compiler's flags treat the fp32 sqrt.
-LAB4D_HD float sqrt_rn(float a) { return (float)sqrt((double)a); }
+using lab4d_rn::sqrt_rn;  // the correctly rounded fp32 square root on both sides (hd_math.hpp)
 
 LAB4D_HD float cand_t(float t0, int k, float dt) { return occ::add_rn(t0, occ::mul_rn((float)k + 0.5f, dt)); }
 

@@ -62,11 +62,6 @@ __global__ void __launch_bounds__(256) k_eik_tangent_input(const float* __restri
   }
 }
 
-inline int pw_grid(long S) {
-  long g = (S + 255) / 256;
-  return (int)(g > 16384 ? 16384 : (g < 1 ? 1 : g));
-}
-
 }  // namespace lab4d
 using namespace lab4d;
 
@@ -74,8 +69,8 @@ extern "C" int lab4d_l2_normalize_forward(const float* x, int S, int C, float* y
   LAB4D_REQUIRE(x && y, "l2_normalize_forward: null pointer");
   LAB4D_REQUIRE(C == 16 || C == 3, "l2_normalize_forward: C must be 16 (feature field) or 3 (got %d)", C);
   if (S == 0) return LAB4D_OK;
-  if (C == 16) hipLaunchKernelGGL((k_l2norm_fwd<16>), dim3(pw_grid(S)), dim3(256), 0, (hipStream_t)stream, x, (long)S, y);
-  else hipLaunchKernelGGL((k_l2norm_fwd<3>), dim3(pw_grid(S)), dim3(256), 0, (hipStream_t)stream, x, (long)S, y);
+  if (C == 16) hipLaunchKernelGGL((k_l2norm_fwd<16>), dim3(grid_1d(S, 256, 16384)), dim3(256), 0, (hipStream_t)stream, x, (long)S, y);
+  else hipLaunchKernelGGL((k_l2norm_fwd<3>), dim3(grid_1d(S, 256, 16384)), dim3(256), 0, (hipStream_t)stream, x, (long)S, y);
   return check_launch("l2_normalize_forward");
 }
 
@@ -83,8 +78,8 @@ extern "C" int lab4d_l2_normalize_backward(const float* x, const float* g, int S
   LAB4D_REQUIRE(x && g && g_x, "l2_normalize_backward: null pointer");
   LAB4D_REQUIRE(C == 16 || C == 3, "l2_normalize_backward: C must be 16 or 3 (got %d)", C);
   if (S == 0) return LAB4D_OK;
-  if (C == 16) hipLaunchKernelGGL((k_l2norm_bwd<16>), dim3(pw_grid(S)), dim3(256), 0, (hipStream_t)stream, x, g, (long)S, g_x);
-  else hipLaunchKernelGGL((k_l2norm_bwd<3>), dim3(pw_grid(S)), dim3(256), 0, (hipStream_t)stream, x, g, (long)S, g_x);
+  if (C == 16) hipLaunchKernelGGL((k_l2norm_bwd<16>), dim3(grid_1d(S, 256, 16384)), dim3(256), 0, (hipStream_t)stream, x, g, (long)S, g_x);
+  else hipLaunchKernelGGL((k_l2norm_bwd<3>), dim3(grid_1d(S, 256, 16384)), dim3(256), 0, (hipStream_t)stream, x, g, (long)S, g_x);
   return check_launch("l2_normalize_backward");
 }
 
@@ -93,6 +88,6 @@ extern "C" int lab4d_eikonal_tangent_input(const float* x, const float* g, const
   LAB4D_REQUIRE(x && g && ge && u, "eikonal_tangent_input: null pointer");
   LAB4D_REQUIRE(L >= 0 && KE >= 6 * L + 3, "eikonal_tangent_input: KE = %d is too small for %d bands", KE, L);
   if (S == 0) return LAB4D_OK;
-  hipLaunchKernelGGL(k_eik_tangent_input, dim3(pw_grid(S)), dim3(256), 0, (hipStream_t)stream, x, g, ge, freq_w, (long)S, L, KE, u);
+  hipLaunchKernelGGL(k_eik_tangent_input, dim3(grid_1d(S, 256, 16384)), dim3(256), 0, (hipStream_t)stream, x, g, ge, freq_w, (long)S, L, KE, u);
   return check_launch("eikonal_tangent_input");
 }

@@ -191,10 +191,7 @@ __global__ void __launch_bounds__(256) k_mat3_inv_bwd(const T* __restrict__ grad
   }
 }
 
-static inline int rows_grid(uint32_t B) {
-  int g = div_up(B, 256);
-  return g < 1 ? 1 : (g > 4096 ? 4096 : g);  // 256 CUs x 16 blocks, grid-stride beyond that
-}
+constexpr int kRowsGridCap = 4096;  // 256 CUs x 16 blocks, grid-stride beyond that
 
 #define LAB4D_DISPATCH(dtype, ...)                                      \
   switch (dtype) {                                                      \
@@ -213,7 +210,7 @@ extern "C" int lab4d_quaternion_mul_forward(const void* in1, const void* in2, vo
   if (B == 0) return LAB4D_OK;  // empty batch: nothing to do (pointers may be null)
   LAB4D_REQUIRE(in1 && in2 && out, "quaternion_mul_forward: null pointer");
   LAB4D_REQUIRE((D1 == 3 || D1 == 4) && (D2 == 3 || D2 == 4), "quaternion_mul_forward: D1,D2 must be 3 or 4 (got %u,%u)", D1, D2);
-  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_qmul_fwd<T>), dim3(rows_grid(B)), dim3(256), 0, (hipStream_t)stream,
+  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_qmul_fwd<T>), dim3(grid_1d(B, 256, kRowsGridCap)), dim3(256), 0, (hipStream_t)stream,
                                            (const T*)in1, (const T*)in2, (T*)out, B, D1, D2));
   return check_launch("quaternion_mul_forward");
 }
@@ -223,7 +220,7 @@ extern "C" int lab4d_quaternion_mul_backward(const void* grad, uint32_t B, uint3
   if (B == 0) return LAB4D_OK;  // empty batch: nothing to do (pointers may be null)
   LAB4D_REQUIRE(grad && in1 && in2 && g1 && g2, "quaternion_mul_backward: null pointer");
   LAB4D_REQUIRE((D1 == 3 || D1 == 4) && (D2 == 3 || D2 == 4), "quaternion_mul_backward: D1,D2 must be 3 or 4");
-  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_qmul_bwd<T>), dim3(rows_grid(B)), dim3(256), 0, (hipStream_t)stream,
+  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_qmul_bwd<T>), dim3(grid_1d(B, 256, kRowsGridCap)), dim3(256), 0, (hipStream_t)stream,
                                            (const T*)grad, B, D1, D2, (const T*)in1, (const T*)in2, (T*)g1, (T*)g2));
   return check_launch("quaternion_mul_backward");
 }
@@ -234,7 +231,7 @@ extern "C" int lab4d_quaternion_mul_backward_backward(const void* go1, const voi
   if (B == 0) return LAB4D_OK;  // empty batch: nothing to do (pointers may be null)
   LAB4D_REQUIRE(go1 && go2 && grad && in1 && in2 && gg && gga && ggb, "quaternion_mul_backward_backward: null pointer");
   LAB4D_REQUIRE((D1 == 3 || D1 == 4) && (D2 == 3 || D2 == 4), "quaternion_mul_backward_backward: D1,D2 must be 3 or 4");
-  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_qmul_bwd_bwd<T>), dim3(rows_grid(B)), dim3(256), 0, (hipStream_t)stream,
+  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_qmul_bwd_bwd<T>), dim3(grid_1d(B, 256, kRowsGridCap)), dim3(256), 0, (hipStream_t)stream,
                                            (const T*)go1, (const T*)go2, B, D1, D2, (const T*)grad, (const T*)in1,
                                            (const T*)in2, (T*)gg, (T*)gga, (T*)ggb));
   return check_launch("quaternion_mul_backward_backward");
@@ -243,7 +240,7 @@ extern "C" int lab4d_quaternion_mul_backward_backward(const void* go1, const voi
 extern "C" int lab4d_quaternion_conjugate(const void* in, uint32_t B, void* out, int dtype, void* stream) {
   if (B == 0) return LAB4D_OK;  // empty batch: nothing to do (pointers may be null)
   LAB4D_REQUIRE(in && out, "quaternion_conjugate: null pointer");
-  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_qconj<T>), dim3(rows_grid(B)), dim3(256), 0, (hipStream_t)stream,
+  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_qconj<T>), dim3(grid_1d(B, 256, kRowsGridCap)), dim3(256), 0, (hipStream_t)stream,
                                            (const T*)in, B, (T*)out));
   return check_launch("quaternion_conjugate");
 }
@@ -251,7 +248,7 @@ extern "C" int lab4d_quaternion_conjugate(const void* in, uint32_t B, void* out,
 extern "C" int lab4d_mat3x3_det_forward(const void* in, void* out, uint32_t B, int dtype, void* stream) {
   if (B == 0) return LAB4D_OK;  // empty batch: nothing to do (pointers may be null)
   LAB4D_REQUIRE(in && out, "mat3x3_det_forward: null pointer");
-  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_mat3<T, 0>), dim3(rows_grid(B)), dim3(256), 0, (hipStream_t)stream,
+  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_mat3<T, 0>), dim3(grid_1d(B, 256, kRowsGridCap)), dim3(256), 0, (hipStream_t)stream,
                                            (const T*)in, (const T*)nullptr, (T*)out, (T*)nullptr, B));
   return check_launch("mat3x3_det_forward");
 }
@@ -259,21 +256,21 @@ extern "C" int lab4d_mat3x3_scale_adjoint_forward(const void* in, const void* sc
                                                   void* stream) {
   if (B == 0) return LAB4D_OK;  // empty batch: nothing to do (pointers may be null)
   LAB4D_REQUIRE(in && scales && out, "mat3x3_scale_adjoint_forward: null pointer");
-  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_mat3<T, 1>), dim3(rows_grid(B)), dim3(256), 0, (hipStream_t)stream,
+  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_mat3<T, 1>), dim3(grid_1d(B, 256, kRowsGridCap)), dim3(256), 0, (hipStream_t)stream,
                                            (const T*)in, (const T*)scales, (T*)out, (T*)nullptr, B));
   return check_launch("mat3x3_scale_adjoint_forward");
 }
 extern "C" int lab4d_mat3x3_inv_forward(const void* in, void* out, void* out_scales, uint32_t B, int dtype, void* stream) {
   if (B == 0) return LAB4D_OK;  // empty batch: nothing to do (pointers may be null)
   LAB4D_REQUIRE(in && out && out_scales, "mat3x3_inv_forward: null pointer");
-  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_mat3<T, 2>), dim3(rows_grid(B)), dim3(256), 0, (hipStream_t)stream,
+  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_mat3<T, 2>), dim3(grid_1d(B, 256, kRowsGridCap)), dim3(256), 0, (hipStream_t)stream,
                                            (const T*)in, (const T*)nullptr, (T*)out, (T*)out_scales, B));
   return check_launch("mat3x3_inv_forward");
 }
 extern "C" int lab4d_mat3x3_inv_backward(const void* grad, const void* inv, void* gin, uint32_t B, int dtype, void* stream) {
   if (B == 0) return LAB4D_OK;  // empty batch: nothing to do (pointers may be null)
   LAB4D_REQUIRE(grad && inv && gin, "mat3x3_inv_backward: null pointer");
-  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_mat3_inv_bwd<T>), dim3(rows_grid(B)), dim3(256), 0, (hipStream_t)stream,
+  LAB4D_DISPATCH(dtype, hipLaunchKernelGGL((k_mat3_inv_bwd<T>), dim3(grid_1d(B, 256, kRowsGridCap)), dim3(256), 0, (hipStream_t)stream,
                                            (const T*)grad, (const T*)inv, (T*)gin, B));
   return check_launch("mat3x3_inv_backward");
 }

@@ -213,7 +213,7 @@ extern "C" int lab4d_ray_samples_forward(const float* hxy, const float* Kinv, co
   LAB4D_REQUIRE((cq == nullptr) == (ct == nullptr), "ray_samples_forward: cam2field q and t must be given together");
   const long S = (long)M * N * D;
   if (S == 0) return LAB4D_OK;
-  int grid = div_up(S, 256); if (grid > 8192) grid = 8192;
+  const int grid = grid_1d(S, 256, 8192);
   hipLaunchKernelGGL(k_ray_samples_fwd, dim3(grid), dim3(256), 0, (hipStream_t)stream, hxy, Kinv, near_far, depth_in, cq, ct,
                      M, N, D, xyz_cam, dir_cam, deltas, depth, xyz_field, dir_field);
   return check_launch("ray_samples_forward");

@@ -1,28 +1,14 @@
 // Per-ray arithmetic of sample_pdf (lab4d/utils/render_utils.py:187-233) in the reference's own order of floating-point operations.
-// Plain C++ behind LAB4D_HD (see fk_math.hpp): csrc/raymarch.hip runs it one thread per ray, tests/host_harness/sample_pdf_host.cpp
+// Plain C++ behind LAB4D_HD (see hd_math.hpp): csrc/raymarch.hip runs it one thread per ray, tests/host_harness/sample_pdf_host.cpp
 // compiles it with g++ (-ffp-contract=off) so that the CPU test-suite can hold it bit for bit to torch's CPU kernels.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define LAB4D_HD __host__ __device__ inline
-#else
-#define LAB4D_HD inline
-#endif
+#include "hd_math.hpp"
 
 namespace lab4d_pdf {
-
-// rounded fp32 sum / product / quotient that must not be contracted into an fma (device: made opaque to the optimiser, see common.hpp)
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ float add_rn(float a, float b) { float p = a + b; asm volatile("" : "+v"(p)); return p; }
-__device__ __forceinline__ float mul_rn(float a, float b) { float p = a * b; asm volatile("" : "+v"(p)); return p; }
-__device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
-#else
-inline float add_rn(float a, float b) { volatile float p = a + b; return p; }
-inline float mul_rn(float a, float b) { volatile float p = a * b; return p; }
-inline float div_rn(float a, float b) { volatile float p = a / b; return p; }
-#endif
+// rounded fp32 sum / product / quotient that must not be contracted into an fma (see hd_math.hpp)
+using lab4d_rn::add_rn;
+using lab4d_rn::div_rn;
+using lab4d_rn::mul_rn;
 
 // torch.sum(x, -1) of a contiguous fp32 row on the CPU, bit for bit: ATen's cascade_sum / vectorized_inner_sum
 // (aten/src/ATen/native/cpu/SumKernel.cpp) keeps 4 independent vector accumulators (ILP) of 8 float lanes (the kernel is built for AVX2 and

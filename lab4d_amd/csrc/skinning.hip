@@ -765,15 +765,14 @@ using namespace lab4d;
              return LAB4D_EINVAL;                                                     \
   }
 
-static inline int sgrid(long n) { int g = div_up(n, 256); return g > 8192 ? 8192 : (g < 1 ? 1 : g); }
 
 extern "C" int lab4d_bone_coords_forward(const float* xyz, const float* ar, const float* ad, const float* gauss, int S, int spf, int M, int B,
                                          float* out, void* stream) {
   LAB4D_REQUIRE(xyz && ar && ad && gauss && out, "bone_coords_forward: null pointer");
   LAB4D_REQUIRE(spf > 0 && (long)M * spf >= S, "bone_coords_forward: M*spf < S");
   if (S == 0) return LAB4D_OK;
-  if (spf % 256 == 0) { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_fwd<NB, true>), dim3(sgrid(S)), dim3(256), 0, (hipStream_t)stream, xyz, ar, ad, gauss, (long)S, spf, out)); }
-  else { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_fwd<NB, false>), dim3(sgrid(S)), dim3(256), 0, (hipStream_t)stream, xyz, ar, ad, gauss, (long)S, spf, out)); }
+  if (spf % 256 == 0) { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_fwd<NB, true>), dim3(grid_1d(S, 256, 8192)), dim3(256), 0, (hipStream_t)stream, xyz, ar, ad, gauss, (long)S, spf, out)); }
+  else { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_fwd<NB, false>), dim3(grid_1d(S, 256, 8192)), dim3(256), 0, (hipStream_t)stream, xyz, ar, ad, gauss, (long)S, spf, out)); }
   return check_launch("bone_coords_forward");
 }
 
@@ -784,8 +783,8 @@ extern "C" int lab4d_bone_coords_backward(const float* xyz, const float* ar, con
   if (S == 0) return LAB4D_OK;
   hipStream_t st = (hipStream_t)stream;
   if (g_xyz) {
-    if (spf % 256 == 0) { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_bwd_x<NB, true, false>), dim3(sgrid(S)), dim3(256), 0, st, ar, gauss, g_bone, (long)S, spf, g_xyz, nullptr, nullptr)); }
-    else { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_bwd_x<NB, false, false>), dim3(sgrid(S)), dim3(256), 0, st, ar, gauss, g_bone, (long)S, spf, g_xyz, nullptr, nullptr)); }
+    if (spf % 256 == 0) { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_bwd_x<NB, true, false>), dim3(grid_1d(S, 256, 8192)), dim3(256), 0, st, ar, gauss, g_bone, (long)S, spf, g_xyz, nullptr, nullptr)); }
+    else { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_bwd_x<NB, false, false>), dim3(grid_1d(S, 256, 8192)), dim3(256), 0, st, ar, gauss, g_bone, (long)S, spf, g_xyz, nullptr, nullptr)); }
   }
   if (g_ar || g_ad || g_gauss) {
     LAB4D_REQUIRE(g_ar && g_ad && g_gauss, "bone_coords_backward: parameter gradients must be requested together");
@@ -803,7 +802,7 @@ extern "C" int lab4d_bone_coords_backward_gram(const float* xyz, const float* ar
   hipStream_t st = (hipStream_t)stream;
   if (int e = zero_async(G, (size_t)M * 3 * B * 4 * sizeof(float), st)) return e;
   if (S == 0) return LAB4D_OK;
-  int grid = sgrid(S); if (grid > 2048) grid = 2048;  // resident blocks: every block ends with 3B x 4 atomics onto the same M x 3B x 4 words
+  const int grid = grid_1d(S, 256, 2048);  // resident blocks: every block ends with 3B x 4 atomics onto the same M x 3B x 4 words
   SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_bwd_x<NB, true, true>), dim3(grid), dim3(256), 0, st, ar, gauss, g_bone, (long)S, spf, g_xyz, xyz, G));
   return check_launch("bone_coords_backward_gram");
 }
@@ -832,8 +831,8 @@ extern "C" int lab4d_skin_blend_forward(const float* xyz, const float* art_r, co
   if (S == 0) return LAB4D_OK;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_bone_affine, dim3(div_up(M * B, 64)), dim3(64), 0, st, art_r, art_d, gauss, M, B, work);
-  if (spf % 256 == 0) { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_blend_fwd<NB, true>), dim3(sgrid(S)), dim3(256), 0, st, xyz, work, raw, sr, sd, (long)S, spf, out, ent, dskin)); }
-  else { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_blend_fwd<NB, false>), dim3(sgrid(S)), dim3(256), 0, st, xyz, work, raw, sr, sd, (long)S, spf, out, ent, dskin)); }
+  if (spf % 256 == 0) { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_blend_fwd<NB, true>), dim3(grid_1d(S, 256, 8192)), dim3(256), 0, st, xyz, work, raw, sr, sd, (long)S, spf, out, ent, dskin)); }
+  else { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_blend_fwd<NB, false>), dim3(grid_1d(S, 256, 8192)), dim3(256), 0, st, xyz, work, raw, sr, sd, (long)S, spf, out, ent, dskin)); }
   return check_launch("skin_blend_forward");
 }
 
@@ -876,7 +875,7 @@ extern "C" int lab4d_skin_blend_backward_acc(const float* xyz, const float* art_
     if (int e = zero_async(Q, (size_t)M * B * 10 * sizeof(float), st)) return e;
   if (fused) {
     // one resident set of blocks walking the samples (every block ends with B x 18 atomics onto the same M x B x 18 words)
-    int grid = sgrid(S); if (grid > 2048) grid = 2048;
+    const int grid = grid_1d(S, 256, 2048);
 #define BLEND_BWD(UNI_, FUSE_, GRID_)                                                                                                              \
   do {                                                                                                                                              \
     if (accumulate) { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_blend_bwd<NB, UNI_, FUSE_, true>), dim3(GRID_), dim3(256), 0, st, xyz, aff, raw, sr, sd, g_out, \
@@ -886,9 +885,9 @@ extern "C" int lab4d_skin_blend_backward_acc(const float* xyz, const float* art_
   } while (0)
     BLEND_BWD(true, true, grid);
   } else if (spf % 256 == 0) {
-    BLEND_BWD(true, false, sgrid(S));
+    BLEND_BWD(true, false, grid_1d(S, 256, 8192));
   } else {
-    BLEND_BWD(false, false, sgrid(S));
+    BLEND_BWD(false, false, grid_1d(S, 256, 8192));
   }
 #undef BLEND_BWD
   if (int e = check_launch("skin_blend_backward")) return e;
@@ -953,7 +952,7 @@ __global__ void __launch_bounds__(256) k_gauss_density_bwd(const float* __restri
 extern "C" int lab4d_gauss_density_forward(const float* xyz, const float* centres, int B, const float* ibeta, int S, float* out, int* best, void* stream) {
   LAB4D_REQUIRE(xyz && centres && out && ibeta, "gauss_density_forward: null pointer");
   if (S == 0) return LAB4D_OK;
-  hipLaunchKernelGGL(lab4d::k_gauss_density_fwd, dim3(sgrid(S)), dim3(256), 0, (hipStream_t)stream, xyz, centres, B, ibeta, (long)S, out, best);
+  hipLaunchKernelGGL(lab4d::k_gauss_density_fwd, dim3(grid_1d(S, 256, 8192)), dim3(256), 0, (hipStream_t)stream, xyz, centres, B, ibeta, (long)S, out, best);
   return check_launch("gauss_density_forward");
 }
 extern "C" int lab4d_gauss_density_backward(const float* xyz, const float* centres, int B, const float* ibeta, const int* best, const float* g, int S,
@@ -961,7 +960,7 @@ extern "C" int lab4d_gauss_density_backward(const float* xyz, const float* centr
   LAB4D_REQUIRE(xyz && centres && best && g && g_centres, "gauss_density_backward: null pointer");
   LAB4D_REQUIRE(B <= 64, "gauss_density_backward: B too large");
   if (S == 0) return LAB4D_OK;
-  int grid = sgrid(S); if (grid > 1024) grid = 1024;
+  const int grid = grid_1d(S, 256, 1024);
   hipLaunchKernelGGL(lab4d::k_gauss_density_bwd, dim3(grid), dim3(256), (3 * B + 1) * sizeof(float), (hipStream_t)stream, xyz, centres, B, ibeta, best, g,
                      (long)S, g_xyz, g_centres, g_ibeta);
   return check_launch("gauss_density_backward");

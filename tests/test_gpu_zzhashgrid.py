@@ -3,7 +3,7 @@ oracle/hashgrid_oracle.py (parity vs the reference is unpinned by nature: the re
 
 First hardware run (round 2) found the kernels 2e-5 off at the finest level (res 2048): the compiler had fused
 `x * res - floor(x * res)` into fma(x, res, -floor), i.e. an UNROUNDED product, which moves the fractional cell position by up
-to ulp(x * res) = 1.2e-4.  The product is now opaque to the optimiser (hashgrid_math.hpp lab4d_mul_rn) and the forward bound
+to ulp(x * res) = 1.2e-4.  The product is now opaque to the optimiser (mul_rn of csrc/hd_math.hpp) and the forward bound
 is a few ulp."""
 import os
 
