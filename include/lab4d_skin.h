@@ -20,7 +20,7 @@
 int lab4d_bone_coords_forward(const float* xyz, const float* art_r, const float* art_d, const float* gauss, int S,
                               int spf, int M, int B, float* xyz_bone, void* stream);
 /* g_bone (S,3B) -> g_xyz (S,3) written; g_art_r, g_art_d (M,B,4), g_gauss (B,3) accumulated (zero-fill first).
- * The three parameter gradients may be NULL: the host then derives them from lab4d_gram_per_frame(g_bone, [xyz,1])
+ * The three parameter gradients may be NULL together (one or two alone are refused before anything is launched): the host then derives them from lab4d_gram_per_frame(g_bone, [xyz,1])
  * (the bone transform is affine in the point), which reads g_bone once instead of once per bone. */
 int lab4d_bone_coords_backward(const float* xyz, const float* art_r, const float* art_d, const float* gauss,
                                const float* g_bone, int S, int spf, int M, int B, float* g_xyz, float* g_art_r,

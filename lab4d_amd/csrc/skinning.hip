@@ -764,6 +764,9 @@ using namespace lab4d;
     default: set_error("skinning kernels are instantiated for B = 25 (bob, skel-quad) and 18 (skel-human); got %d", B); \
              return LAB4D_EINVAL;                                                     \
   }
+// for the entries that launch something (a table kernel, a zero-fill) ahead of their SKIN_DISPATCH: refuse before the first launch
+#define SKIN_REQUIRE_BONES(B) \
+  LAB4D_REQUIRE((B) == 25 || (B) == 18, "skinning kernels are instantiated for B = 25 (bob, skel-quad) and 18 (skel-human); got %d", B)
 
 
 extern "C" int lab4d_bone_coords_forward(const float* xyz, const float* ar, const float* ad, const float* gauss, int S, int spf, int M, int B,
@@ -780,14 +783,14 @@ extern "C" int lab4d_bone_coords_backward(const float* xyz, const float* ar, con
                                           int spf, int M, int B, float* g_xyz, float* g_ar, float* g_ad, float* g_gauss, void* stream) {
   LAB4D_REQUIRE(xyz && ar && ad && gauss && g_bone, "bone_coords_backward: null pointer");
   LAB4D_REQUIRE(spf > 0 && (long)M * spf >= S, "bone_coords_backward: M*spf < S");
+  LAB4D_REQUIRE((g_ar && g_ad && g_gauss) || !(g_ar || g_ad || g_gauss), "bone_coords_backward: parameter gradients must be requested together");
   if (S == 0) return LAB4D_OK;
   hipStream_t st = (hipStream_t)stream;
   if (g_xyz) {
     if (spf % 256 == 0) { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_bwd_x<NB, true, false>), dim3(grid_1d(S, 256, 8192)), dim3(256), 0, st, ar, gauss, g_bone, (long)S, spf, g_xyz, nullptr, nullptr)); }
     else { SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_bwd_x<NB, false, false>), dim3(grid_1d(S, 256, 8192)), dim3(256), 0, st, ar, gauss, g_bone, (long)S, spf, g_xyz, nullptr, nullptr)); }
   }
-  if (g_ar || g_ad || g_gauss) {
-    LAB4D_REQUIRE(g_ar && g_ad && g_gauss, "bone_coords_backward: parameter gradients must be requested together");
+  if (g_ar) {
     const int chunk = 8192;
     const dim3 grid(div_up(spf, chunk), M);
     SKIN_DISPATCH(B, hipLaunchKernelGGL((k_bone_bwd_p<NB>), grid, dim3(256), 0, st, xyz, ar, ad, gauss, g_bone, (long)S, spf, chunk, g_ar, g_ad, g_gauss));
@@ -799,6 +802,7 @@ extern "C" int lab4d_bone_coords_backward_gram(const float* xyz, const float* ar
                                                float* g_xyz, float* G, void* stream) {
   LAB4D_REQUIRE(xyz && ar && gauss && g_bone && g_xyz && G, "bone_coords_backward_gram: null pointer");
   LAB4D_REQUIRE(spf > 0 && spf % 256 == 0 && (long)M * spf >= S, "bone_coords_backward_gram: needs spf %% 256 == 0 and M*spf >= S (got spf=%d)", spf);
+  SKIN_REQUIRE_BONES(B);
   hipStream_t st = (hipStream_t)stream;
   if (int e = zero_async(G, (size_t)M * 3 * B * 4 * sizeof(float), st)) return e;
   if (S == 0) return LAB4D_OK;
@@ -828,6 +832,7 @@ extern "C" int lab4d_skin_blend_forward(const float* xyz, const float* art_r, co
                                         float* work, void* stream) {
   LAB4D_REQUIRE(xyz && art_r && art_d && gauss && raw && sr && sd && out && work, "skin_blend_forward: null pointer");
   LAB4D_REQUIRE(spf > 0 && (long)M * spf >= S, "skin_blend_forward: M*spf < S");
+  SKIN_REQUIRE_BONES(B);
   if (S == 0) return LAB4D_OK;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_bone_affine, dim3(div_up(M * B, 64)), dim3(64), 0, st, art_r, art_d, gauss, M, B, work);
@@ -860,6 +865,7 @@ extern "C" int lab4d_skin_blend_backward_acc(const float* xyz, const float* art_
                                              float* g_gauss, float* work, int accumulate, void* stream) {
   LAB4D_REQUIRE(xyz && art_r && art_d && gauss && raw && sr && sd && g_out && g_xyz && g_raw && work, "skin_blend_backward: null pointer");
   LAB4D_REQUIRE(spf > 0 && (long)M * spf >= S, "skin_blend_backward: M*spf < S");
+  SKIN_REQUIRE_BONES(B);
   if (S == 0) return LAB4D_OK;
   hipStream_t st = (hipStream_t)stream;
   // work = [aff (M,B,12) | Q (M,B,10) | G (M,B,12)] and, for the unfused path only, behind them [coef (S,B) | gw (S,8) | gsk (S,B) | xx (S,10)];
@@ -957,7 +963,7 @@ extern "C" int lab4d_gauss_density_forward(const float* xyz, const float* centre
 }
 extern "C" int lab4d_gauss_density_backward(const float* xyz, const float* centres, int B, const float* ibeta, const int* best, const float* g, int S,
                                             float* g_xyz, float* g_centres, float* g_ibeta, void* stream) {
-  LAB4D_REQUIRE(xyz && centres && best && g && g_centres, "gauss_density_backward: null pointer");
+  LAB4D_REQUIRE(xyz && centres && ibeta && best && g && g_centres, "gauss_density_backward: null pointer");
   LAB4D_REQUIRE(B <= 64, "gauss_density_backward: B too large");
   if (S == 0) return LAB4D_OK;
   const int grid = grid_1d(S, 256, 1024);
