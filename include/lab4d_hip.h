@@ -290,6 +290,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_hashsdf.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 16. Pruning of the packed sample list by transmittance and opacity, between a density pass without gradients and the differentiable
+ *     field (not in the reference, parity unpinned).  See lab4d_prune.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_prune.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,9 @@ Empty-space skipping: an occgrid.OccupancyGrid (a bit per cell of a coarse grid 
 field's density with update_occupancy() and handed to forward_compacted(occ=...), whose compaction then also drops the samples in empty cells;
 grid.ray_depths() places a ray's samples between its first and last occupied cell.  render_packed() goes all the way: the rays are marched at a
 fixed step through the occupied cells only (packed.march), the field runs on the packed list of kept samples, and the list is composited per ray
-(packed.composite); nothing of size rays x samples-per-ray exists.  All of it is opt-in.
+(packed.composite); nothing of size rays x samples-per-ray exists.  render_packed_pruned() also drops the rows BEHIND the surface before the
+differentiable field runs: density() of the kept rows without gradients, packed.prune by transmittance and opacity, forward() on the survivors
+(include/lab4d_prune.h).  All of it is opt-in.
 
 The SDF as an SDF: sdf_gradient() returns the sdf with its gradient in the point from one fused kernel (hashsdf.py, include/lab4d_hashsdf.h),
 differentiable in the table and the geometry net; eikonal_loss() and normals() build on it (the counterparts of nnutils/nerf.py:416-493), and
@@ -178,4 +180,43 @@ def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32
         fields["normal"] = normals(P, cfg, rays.xyz, res=res)
     rendered, mask = packed.composite(dens_s, rays.deltas, fields, rays)
     out = (rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow)
+    return out + (rendered["normal"],) if with_normal else out
+
+
+def density(P, cfg, xyz, prec=mlp.PREC_F32, res=None):
+    """xyz (S,3) -> density (S,1): forward()'s encoding (inside_only), geometry chain and volsdf_density, masked outside the box -- without
+    the colour net, for a pass that only asks where a ray becomes opaque (render_packed_pruned).  The per-sample arithmetic is forward()'s
+    own: the same rows give, bit for bit, the density forward() returns at the same precision."""
+    if cfg["L"] * cfg["F"] != 32:
+        raise NotImplementedError("hash field: the geometry net is instantiated for L*F = 32 hash features")
+    lo, hi = P["aabb"][0], P["aabb"][1]
+    x01 = (xyz - lo) / (hi - lo)
+    if res is None:
+        res = resolutions(cfg, xyz.device)
+    enc = hashgrid.hash_encode(x01, P["hash.table"], res, cfg["log2_T"], inside_only=True)
+    geo = mlp.run_chain(mlp.NET_HASH_GEO, prec, P, enc, max(int(xyz.shape[0]), 1))
+    inside = ((x01 >= 0) & (x01 <= 1)).all(-1, keepdim=True).to(geo.dtype)
+    return volsdf_density(geo[:, :1], P["logibeta"]) * inside
+
+
+def render_packed_pruned(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None, with_normal=False,
+                         early_stop_eps=1e-4, alpha_thre=0.0, prune_cap=None):
+    """render_packed() with the rows behind the surface dropped before the differentiable field runs (include/lab4d_prune.h), the two-pass form of
+    Mueller et al. 2022 and nerfacc: packed.march as in render_packed; density() of the kept rows under no_grad; packed.prune drops every row at
+    and behind the point where its ray's transmittance has fallen below early_stop_eps, and every row whose opacity lies below alpha_thre;
+    forward() runs on the survivors (at most prune_cap rows, default cap; STATIC like cap) and packed.composite renders them with the pruned
+    (start, count).  With alpha_thre = 0 what is dropped of a ray weighs less than early_stop_eps in total.  Returns (rgb, mask, depth, total,
+    overflow, kept, kept_overflow): the first five as in render_packed (total / overflow are the march's), kept (1,) int32 = the survivors before
+    prune_cap, kept_overflow (1,) bool = kept > prune_cap; `normal` is appended last with with_normal=True.  Gradients flow to the table, the
+    Linears and logibeta through the surviving rows only: the prune decision itself is not differentiable."""
+    rays = packed.march(grid, origin, dir, t_range, dt, cap, k_max=k_max)
+    with torch.no_grad():
+        dens0 = density(P, cfg, rays.xyz, prec=prec, res=res)
+    kept = packed.prune(rays, dens0, early_stop_eps=early_stop_eps, alpha_thre=alpha_thre, cap=prune_cap, aabb=grid.aabb)
+    rgb_s, dens_s = forward(P, cfg, kept.xyz, kept.dirs, spf=max(kept.cap, 1), prec=prec, res=res, table_grad_f16=table_grad_f16)
+    fields = {"rgb": rgb_s, "depth": kept.t[:, None]}
+    if with_normal:
+        fields["normal"] = normals(P, cfg, kept.xyz, res=res)
+    rendered, mask = packed.composite(dens_s, kept.deltas, fields, kept)
+    out = (rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow, kept.total, kept.overflow)
     return out + (rendered["normal"],) if with_normal else out

@@ -1,9 +1,12 @@
 """Packed ray marching and ragged compositing of the hash field (include/lab4d_packed.h, csrc/packed.hip): `march` steps every ray at a fixed
 step through the occupied cells of an occgrid.OccupancyGrid and emits the kept samples of all rays as ONE packed list with a per-ray
 (start, count); `composite` renders that list directly.  Nothing of size rays x samples-per-ray exists.  The reference has no counterpart
-(nnutils/nerf.py:98 is a TODO); the rules are written down in the header and in csrc/packed_math.hpp.  Nothing here synchronises with the
-host: every call can be captured in a hipGraph."""
+(nnutils/nerf.py:98 is a TODO); the rules are written down in the header and in csrc/packed_math.hpp.  `prune` (include/lab4d_prune.h,
+csrc/prune.hip) drops the rows of such a list that lie behind the point where their ray has become opaque, and the rows without opacity,
+given the density of the rows: the step between a density pass without gradients and the differentiable field.  Nothing here synchronises
+with the host: every call can be captured in a hipGraph."""
 import math
+import struct
 
 import torch
 from torch.autograd import Function
@@ -144,3 +147,76 @@ def composite(density, deltas, fields, rays, modes=None):
         rendered[k] = out[:, co] if m == 2 else out[:, co:co + c]
         co += c
     return rendered, mask
+
+
+# ---------------------------------------------------------------------------------------------------
+# pruning by transmittance and opacity (include/lab4d_prune.h, csrc/prune.hip)
+# ---------------------------------------------------------------------------------------------------
+class PrunedRays(PackedRays):
+    """The packed list of one prune: a PackedRays (total / overflow / cap are the prune's own) that also carries src_row (cap,) int32, the
+    row of the pruned list's source that every surviving row was copied from (-1 in the parked rows): what a caller gathers through to
+    reuse anything it already computed per row."""
+    __slots__ = ("src_row",)
+
+    def __init__(self, **kw):
+        for k in PackedRays.__slots__ + self.__slots__:
+            setattr(self, k, kw[k])
+
+
+def _as_f32(x):
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def prune_thresholds(early_stop_eps, alpha_thre):
+    """The two user-facing values in the tau domain, converted in double precision and rounded to fp32 once (the kernels never call exp):
+    tau_stop = -log(early_stop_eps), +inf for 0: a ray stops where its transmittance has fallen below early_stop_eps;
+    tau_min = -log1p(-alpha_thre): a row is dropped when its opacity 1 - exp(-tau) lies below alpha_thre.  Both must lie in [0, 1)."""
+    eps, alpha = float(early_stop_eps), float(alpha_thre)
+    if not 0.0 <= eps < 1.0:
+        raise RuntimeError("lab4d_amd.packed.prune: early_stop_eps = %r outside [0, 1)" % early_stop_eps)
+    if not 0.0 <= alpha < 1.0:
+        raise RuntimeError("lab4d_amd.packed.prune: alpha_thre = %r outside [0, 1)" % alpha_thre)
+    return (_as_f32(-math.log(eps)) if eps > 0.0 else math.inf), _as_f32(-math.log1p(-alpha))
+
+
+@torch.no_grad()
+def prune(rays, density, early_stop_eps=1e-4, alpha_thre=0.0, cap=None, *, aabb):
+    """rays: a PackedRays; density (P,) or (P,1) float32 on its rows (detached here: the decision is not differentiable); aabb: the box
+    (2,3) / (6,) float32 the list was marched in (grid.aabb) -- the park point of the rows behind the count, which a PackedRays does not
+    carry.  Drops every row at and behind the first row of its ray whose transmittance in front of it, exp(-sum of tau before it), lies
+    below early_stop_eps, and every row whose opacity 1 - exp(-tau) lies below alpha_thre (rules: include/lab4d_prune.h).
+    -> PrunedRays with `cap` rows (default rays.cap), laid out like a march's.  Two kernels (count, write) around one prefix sum; no
+    read-back."""
+    tau_stop, tau_min = prune_thresholds(early_stop_eps, alpha_thre)
+    cap = rays.cap if cap is None else int(cap)
+    if not 0 <= cap < 1 << 31:
+        raise RuntimeError("lab4d_amd.packed.prune: cap = %d outside [0, 2^31)" % cap)
+    P, R = rays.t.shape[0], rays.ray_start.shape[0]
+    _lib.require_device(density, aabb, rays.t, rays.deltas, rays.xyz, rays.dirs, rays.ray_start, rays.ray_count)
+    if density.numel() != P or density.dtype != torch.float32 or density.ndim not in (1, 2):
+        raise RuntimeError("lab4d_amd.packed.prune: density must be float32 (%d,) or (%d, 1), got %s %s" % (P, P, density.dtype, tuple(density.shape)))
+    if aabb.numel() != 6 or aabb.dtype != torch.float32:
+        raise RuntimeError("lab4d_amd.packed.prune: aabb must be float32 (2, 3) or (6,), got %s %s" % (aabb.dtype, tuple(aabb.shape)))
+    _f32("rays.t", rays.t)
+    _f32("rays.deltas", rays.deltas)
+    _f32("rays.xyz", rays.xyz, 3)
+    _f32("rays.dirs", rays.dirs, 3)
+    rs, rc = rays.ray_start, rays.ray_count
+    if rs.dtype != torch.int32 or rc.dtype != torch.int32 or rs.ndim != 1 or rs.shape != rc.shape:
+        raise RuntimeError("lab4d_amd.packed.prune: ray_start / ray_count must be int32 (R,)")
+    if rays.deltas.shape[0] != P or rays.xyz.shape[0] != P or rays.dirs.shape[0] != P:
+        raise RuntimeError("lab4d_amd.packed.prune: t, deltas, xyz and dirs disagree on the number of rows")
+    dev = density.device
+    density = density.detach().reshape(P)
+    keep = torch.zeros(P, dtype=torch.uint8, device=dev)  # (zeros: the rows that no ray owns are not written)
+    count = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.call("packed_prune_count", density, rays.deltas, rs, rc, R, P, tau_stop, tau_min, keep, count)
+    start = torch.cumsum(count, 0, dtype=torch.int32) - count  # (the exclusive scan: at most P < 2^31 survivors)
+    out = {"t": torch.empty(cap, device=dev), "deltas": torch.empty(cap, device=dev), "xyz": torch.empty(cap, 3, device=dev),
+           "dirs": torch.empty(cap, 3, device=dev), "ray_idx": torch.empty(cap, dtype=torch.int32, device=dev),
+           "src_row": torch.empty(cap, dtype=torch.int32, device=dev), "ray_count": torch.empty(R, dtype=torch.int32, device=dev),
+           "total": torch.empty(1, dtype=torch.int32, device=dev)}
+    overflow = torch.empty(1, dtype=torch.uint8, device=dev)
+    _lib.call("packed_prune_write", keep, rs, rc, start, R, P, cap, aabb, rays.t, rays.deltas, rays.xyz, rays.dirs, out["t"], out["deltas"], out["xyz"],
+              out["dirs"], out["ray_idx"], out["src_row"], out["ray_count"], out["total"], overflow)
+    return PrunedRays(ray_start=start, overflow=overflow.view(torch.bool), R=R, cap=cap, **out)
