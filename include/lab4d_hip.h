@@ -296,6 +296,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_prune.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 17. Distortion loss of the packed sample list, forward and adjoint: a prefix scan per ray on the compositor's partition (not in the
+ *     reference, parity unpinned).  See lab4d_distort.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_distort.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,7 @@
 // packed_math.hpp (over occgrid_math.hpp), shared with the CPU twin tests/host_harness/packed_host.cpp, to which the two march kernels are
 // held word for word.  Nothing here reads back or allocates: every entry point can be captured in a hipGraph.
 #include "common.hpp"
+#include "packed_chunk.hpp"
 #include "packed_math.hpp"
 
 namespace lab4d {
@@ -89,19 +90,7 @@ __device__ __forceinline__ RayRows rows_of(const int32_t* __restrict__ ray_start
   return {s, (int)n};
 }
 
-struct ChunkWeights {
-  float w, T;
-};
-// carry: sum of tau over the chunks before this one on entry, this one included on exit
-__device__ __forceinline__ ChunkWeights chunk_weights(const float* __restrict__ density, const float* __restrict__ deltas, long row, bool live, int lane,
-                                                      float& carry) {
-  const float tau = live ? density[row] * deltas[row] : 0.f;
-  const float incl = wave_scan_incl(tau, lane) + carry;
-  float excl = __shfl_up(incl, 1, 64);
-  if (lane == 0) excl = carry;
-  carry = __shfl(incl, 63, 64);
-  return {live ? pk::weight_of(tau, excl) : 0.f, pk::transmit_of(incl)};
-}
+// (ChunkWeights / chunk_weights, a chunk's w_i and T_i from the scan of tau: packed_chunk.hpp, shared with distort.hip)
 
 // Output channel c of a ray is accumulated by lane c (sum channels <= 64), so that the result leaves in one coalesced store.
 __global__ void __launch_bounds__(256) k_packed_composite_fwd(const float* __restrict__ density, const float* __restrict__ deltas, lab4d_field_list fl,

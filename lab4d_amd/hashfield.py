@@ -17,7 +17,8 @@ grid.ray_depths() places a ray's samples between its first and last occupied cel
 fixed step through the occupied cells only (packed.march), the field runs on the packed list of kept samples, and the list is composited per ray
 (packed.composite); nothing of size rays x samples-per-ray exists.  render_packed_pruned() also drops the rows BEHIND the surface before the
 differentiable field runs: density() of the kept rows without gradients, packed.prune by transmittance and opacity, forward() on the survivors
-(include/lab4d_prune.h).  All of it is opt-in.
+(include/lab4d_prune.h).  with_distortion=True on either adds the distortion loss of the list per ray (include/lab4d_distort.h).  All of it
+is opt-in.
 
 The SDF as an SDF: sdf_gradient() returns the sdf with its gradient in the point from one fused kernel (hashsdf.py, include/lab4d_hashsdf.h),
 differentiable in the table and the geometry net; eikonal_loss() and normals() build on it (the counterparts of nnutils/nerf.py:416-493), and
@@ -163,7 +164,14 @@ def normals(P, cfg, xyz, res=None):
     return F.normalize(sdf_gradient(P, cfg, xyz.detach(), res=res)[1], dim=-1)
 
 
-def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None, with_normal=False):
+def _packed_distortion(dens_s, rays, dt):
+    """The distortion loss (R,1) of a marched or pruned list in metric units, so that it does not depend on the length of `dir`: a row's
+    interval is one step, width = rays.deltas = dt |d|, around mid = rays.t * rays.deltas / dt = t |d|."""
+    return packed.distortion(dens_s, rays.deltas, rays.t * rays.deltas / dt, rays.deltas, rays)[:, None]
+
+
+def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None, with_normal=False,
+                  with_distortion=False):
     """Renders rays through the hash field with packed marching (include/lab4d_packed.h): packed.march(grid, origin, dir, t_range, dt, cap, k_max)
     keeps the candidates t0 + (k + 0.5) dt of every ray whose cell's bit is set -- what forward_compacted(occ=grid) keeps of the same lattice --
     as one packed list of at most `cap` rows (STATIC: the call is capturable), forward() runs on those rows (the parked rows behind the count lie
@@ -172,7 +180,9 @@ def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32
     total > cap: samples were dropped, callers check it where they synchronise anyway).  A ray without a kept sample renders zeros.  Gradients flow
     to the table, the Linears and logibeta.
     with_normal=True: normals() of the kept rows is composited like the colour and `normal (R,3)` is appended to the returned tuple (the
-    weighted mean of unit normals: not renormalised; gradients reach it through the weights only).  The other five are unchanged."""
+    weighted mean of unit normals: not renormalised; gradients reach it through the weights only).  The other five are unchanged.
+    with_distortion=True: `distortion (R,1)`, packed.distortion of the kept rows in metric units (width = dt |dir|, mid = t |dir|), is appended
+    LAST, behind `normal` when both are set; gradients reach the table, the geometry Linears and logibeta through the density."""
     rays = packed.march(grid, origin, dir, t_range, dt, cap, k_max=k_max)
     rgb_s, dens_s = forward(P, cfg, rays.xyz, rays.dirs, spf=max(int(cap), 1), prec=prec, res=res, table_grad_f16=table_grad_f16)
     fields = {"rgb": rgb_s, "depth": rays.t[:, None]}
@@ -180,7 +190,9 @@ def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32
         fields["normal"] = normals(P, cfg, rays.xyz, res=res)
     rendered, mask = packed.composite(dens_s, rays.deltas, fields, rays)
     out = (rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow)
-    return out + (rendered["normal"],) if with_normal else out
+    if with_normal:
+        out += (rendered["normal"],)
+    return out + (_packed_distortion(dens_s, rays, dt),) if with_distortion else out
 
 
 def density(P, cfg, xyz, prec=mlp.PREC_F32, res=None):
@@ -200,15 +212,16 @@ def density(P, cfg, xyz, prec=mlp.PREC_F32, res=None):
 
 
 def render_packed_pruned(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None, with_normal=False,
-                         early_stop_eps=1e-4, alpha_thre=0.0, prune_cap=None):
+                         early_stop_eps=1e-4, alpha_thre=0.0, prune_cap=None, with_distortion=False):
     """render_packed() with the rows behind the surface dropped before the differentiable field runs (include/lab4d_prune.h), the two-pass form of
     Mueller et al. 2022 and nerfacc: packed.march as in render_packed; density() of the kept rows under no_grad; packed.prune drops every row at
     and behind the point where its ray's transmittance has fallen below early_stop_eps, and every row whose opacity lies below alpha_thre;
     forward() runs on the survivors (at most prune_cap rows, default cap; STATIC like cap) and packed.composite renders them with the pruned
     (start, count).  With alpha_thre = 0 what is dropped of a ray weighs less than early_stop_eps in total.  Returns (rgb, mask, depth, total,
     overflow, kept, kept_overflow): the first five as in render_packed (total / overflow are the march's), kept (1,) int32 = the survivors before
-    prune_cap, kept_overflow (1,) bool = kept > prune_cap; `normal` is appended last with with_normal=True.  Gradients flow to the table, the
-    Linears and logibeta through the surviving rows only: the prune decision itself is not differentiable."""
+    prune_cap, kept_overflow (1,) bool = kept > prune_cap; `normal` is appended with with_normal=True, and behind it `distortion (R,1)` with
+    with_distortion=True: render_packed's, on the pruned list's own rows.  Gradients flow to the table, the Linears and logibeta through the
+    surviving rows only: the prune decision itself is not differentiable."""
     rays = packed.march(grid, origin, dir, t_range, dt, cap, k_max=k_max)
     with torch.no_grad():
         dens0 = density(P, cfg, rays.xyz, prec=prec, res=res)
@@ -219,4 +232,6 @@ def render_packed_pruned(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.P
         fields["normal"] = normals(P, cfg, kept.xyz, res=res)
     rendered, mask = packed.composite(dens_s, kept.deltas, fields, kept)
     out = (rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow, kept.total, kept.overflow)
-    return out + (rendered["normal"],) if with_normal else out
+    if with_normal:
+        out += (rendered["normal"],)
+    return out + (_packed_distortion(dens_s, kept, dt),) if with_distortion else out

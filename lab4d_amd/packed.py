@@ -3,7 +3,8 @@ step through the occupied cells of an occgrid.OccupancyGrid and emits the kept s
 (start, count); `composite` renders that list directly.  Nothing of size rays x samples-per-ray exists.  The reference has no counterpart
 (nnutils/nerf.py:98 is a TODO); the rules are written down in the header and in csrc/packed_math.hpp.  `prune` (include/lab4d_prune.h,
 csrc/prune.hip) drops the rows of such a list that lie behind the point where their ray has become opaque, and the rows without opacity,
-given the density of the rows: the step between a density pass without gradients and the differentiable field.  Nothing here synchronises
+given the density of the rows: the step between a density pass without gradients and the differentiable field.  `distortion`
+(include/lab4d_distort.h, csrc/distort.hip) is the distortion loss of such a list per ray, with its adjoint.  Nothing here synchronises
 with the host: every call can be captured in a hipGraph."""
 import math
 import struct
@@ -220,3 +221,43 @@ def prune(rays, density, early_stop_eps=1e-4, alpha_thre=0.0, cap=None, *, aabb)
     _lib.call("packed_prune_write", keep, rs, rc, start, R, P, cap, aabb, rays.t, rays.deltas, rays.xyz, rays.dirs, out["t"], out["deltas"], out["xyz"],
               out["dirs"], out["ray_idx"], out["src_row"], out["ray_count"], out["total"], overflow)
     return PrunedRays(ray_start=start, overflow=overflow.view(torch.bool), R=R, cap=cap, **out)
+
+
+# ---------------------------------------------------------------------------------------------------
+# distortion loss (include/lab4d_distort.h, csrc/distort.hip)
+# ---------------------------------------------------------------------------------------------------
+class _PackedDistortion(Function):
+    @staticmethod
+    def forward(ctx, density, deltas, mid, width, ray_start, ray_count):
+        P, R = density.shape[0], ray_start.shape[0]
+        loss = torch.empty(R, device=density.device)
+        _lib.call("packed_distortion_forward", density, deltas, mid, width, ray_start, ray_count, R, P, loss)
+        ctx.save_for_backward(density, deltas, mid, width, ray_start, ray_count)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss):
+        density, deltas, mid, width, ray_start, ray_count = ctx.saved_tensors
+        P, R = density.shape[0], ray_start.shape[0]
+        g_density = torch.zeros_like(density) if ctx.needs_input_grad[0] else None  # (zeros: the rows that no ray owns are not written)
+        g_deltas = torch.zeros_like(deltas) if ctx.needs_input_grad[1] else None
+        _lib.call("packed_distortion_backward", density, deltas, mid, width, ray_start, ray_count, R, P, g_loss.contiguous(), g_density, g_deltas)
+        return g_density, g_deltas, None, None, None, None
+
+
+def distortion(density, deltas, mid, width, rays):
+    """The distortion loss of Barron et al. 2022 (mip-NeRF 360) per ray of a packed list (rules: include/lab4d_distort.h):
+    sum_i sum_j w_i w_j |mid_i - mid_j| + (1/3) sum_i w_i^2 width_i with the weights w that `composite` forms from the same density and
+    deltas.  density, deltas, mid, width: float32 (P,) or (P,1) on the packed rows of `rays` (a PackedRays, or anything with ray_start /
+    ray_count (R,) int32); mid is a row's interval midpoint, ascending within a ray, width >= 0 its width in the units of mid.  -> (R,); a
+    ray without samples gives 0.  Differentiable (once) in density and deltas; mid and width are detached."""
+    rs, rc = rays.ray_start, rays.ray_count
+    _lib.require_device(density, deltas, mid, width, rs, rc)
+    P = density.shape[0]
+    for name, x in (("density", density), ("deltas", deltas), ("mid", mid), ("width", width)):
+        if x.numel() != P or x.dtype != torch.float32 or x.ndim not in (1, 2):
+            raise RuntimeError("lab4d_amd.packed.distortion: %s must be float32 (%d,) or (%d, 1), got %s %s" % (name, P, P, x.dtype, tuple(x.shape)))
+    if rs.dtype != torch.int32 or rc.dtype != torch.int32 or rs.ndim != 1 or rs.shape != rc.shape:
+        raise RuntimeError("lab4d_amd.packed.distortion: ray_start / ray_count must be int32 (R,)")
+    return _PackedDistortion.apply(density.reshape(P), deltas.reshape(P), mid.detach().reshape(P), width.detach().reshape(P), rs, rc)
