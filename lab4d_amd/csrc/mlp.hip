@@ -302,6 +302,11 @@ __global__ void __launch_bounds__(256) k_mlp_wgrad_big(const typename P::store_t
 // the compiler cannot tell which LDS bytes a DMA writes, so it drained every DMA (s_waitcnt vmcnt(0)) before the first
 // ds_read of the other stage.  Here the LDS reads are inline asm (invisible to that analysis), the waits are explicit
 // counted vmcnt / lgkmcnt, and the barrier is the raw s_barrier (no fence).
+// The matrix side is software-pipelined (see the loop): the fragment reads of a 16-sample sub-step are issued while the MFMAs of the
+// sub-step before it run, across the stage boundary too, each set retired by a counted lgkmcnt; the refill DMA goes out before the
+// barrier wait, not after it; the bias row sums of the layers are one small MFMA per A tile instead of ~32 VALU operations per
+// sub-step.  With operands served from L2 the 256 x 256 core went from 2.19 to 1.93 ms at 16.78 M samples, the kernel from 3.22 to
+// 2.90 ms (profiles/wgrad_ring_pipeline.json).  Every accumulator still receives the same MFMAs in the same order.
 __device__ __forceinline__ void dma_1k(const void* gsrc_lane, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) unsigned int*)gsrc_lane,
                                    (__attribute__((address_space(3))) unsigned int*)lds_wave_base, 16, 0, 0);
@@ -312,6 +317,9 @@ __device__ __forceinline__ u32x4_t lds_read16(unsigned addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
   return v;
 }
+
+template <int V>
+using IC = std::integral_constant<int, V>;
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -340,7 +348,10 @@ __global__ void __launch_bounds__(64 * NW) k_mlp_wgrad_dma(const unsigned short*
   constexpr int NS0 = 65536 / STAGE, NSTAGE = NS0 < 4 ? 4 : (NS0 > 8 ? 8 : NS0);  // ring depth: >= 64 KiB in flight per CU
   constexpr int PA = (2 * MT + NW - 1) / NW, PB = (4 * NBW + NW - 1) / NW, PW = PA + PB;  // transfers per wave per stage (exact: the counted waits rely on it)
   static_assert(PA * NW == 2 * MT || MT == 1, "A pieces per wave (MT = 1: two pieces, the other waves re-fetch the last one)");
+  constexpr int AHEAD = NSTAGE - 1;  // stages the prologue issues; the last buffer takes the first refill
+  constexpr bool DB_MFMA = WC == 2;  // bias row sums on the matrix pipe (the heads keep the VALU sums, bit for bit)
   static_assert(PW * (NSTAGE - 2) <= 63, "vmcnt range");
+  static_assert(TM + TN <= 15, "lgkmcnt range");
   static_assert(NSTAGE * STAGE <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(16))) unsigned char lds[NSTAGE * STAGE];
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), row = lane & 31, h = lane >> 5;
@@ -376,8 +387,12 @@ __global__ void __launch_bounds__(64 * NW) k_mlp_wgrad_dma(const unsigned short*
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
   float rs[TM];
+  f32x4_t dbacc[TM];
 #pragma unroll
-  for (int i = 0; i < TM; ++i) rs[i] = 0.f;
+  for (int i = 0; i < TM; ++i) {
+    rs[i] = 0.f;
+    dbacc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
 
   // LDS image of a stage operand: [rows][64 B]; row r keeps its 16-byte chunk c (4 per row) at slot c ^ ((r >> 2) & 3).
   // The DMA writes lane-linear (a 1-KiB piece = 16 rows, position = lane), so the swizzle is applied to the SOURCE chunk
@@ -416,28 +431,44 @@ __global__ void __launch_bounds__(64 * NW) k_mlp_wgrad_dma(const unsigned short*
   const unsigned f = (row >> 2) & 3;
   const unsigned la0 = lds_base + (unsigned)((wr * TM * 32 + row) * 64) + ((unsigned)(h ^ f) * 16u);  // sub-step 0: chunk h
   const unsigned lb0 = lds_base + (unsigned)A_BYTES + (unsigned)((wc * TN * 32 + row) * 64) + ((unsigned)(h ^ f) * 16u);
-  auto compute = [&](int buf) {
-    const unsigned oa = la0 + (unsigned)buf * STAGE, ob = lb0 + (unsigned)buf * STAGE;
+  // Fragment reads of sub-step `SUB` (16 samples) of the stage in `buf`: chunk 2*SUB + h -> slot (2*SUB + h) ^ f = slot(sub 0) ^ (2*SUB),
+  // i.e. byte address ^ 32.  Asm the compiler cannot see through: every destination is tied to the counted wait that retires it.
+  auto read_frags = [&](int buf, auto subc, u32x4_t (&a4)[TM], u32x4_t (&b4)[TN]) {
+    constexpr unsigned X = 32u * decltype(subc)::value;
+    const unsigned xa = (la0 + (unsigned)buf * STAGE) ^ X, xb = (lb0 + (unsigned)buf * STAGE) ^ X;
+    sfor<0, TM>([&](auto ic) { a4[decltype(ic)::value] = lds_read16<decltype(ic)::value * 2048>(xa); });
+    sfor<0, TN>([&](auto jc) { b4[decltype(jc)::value] = lds_read16<decltype(jc)::value * 2048>(xb); });
+  };
+  // wait until at most CNT LDS reads (the TM + TN of the OTHER fragment set, issued later) are outstanding: this set has landed
+  auto wait_frags = [&](auto cntc, u32x4_t (&a4)[TM], u32x4_t (&b4)[TN]) {
+    constexpr int CNT = decltype(cntc)::value;
+    if constexpr (TM == 4) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a4[0]), "+v"(a4[1]), "+v"(a4[2]), "+v"(a4[3]) : "n"(CNT));
+    else if constexpr (TM == 2) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a4[0]), "+v"(a4[1]) : "n"(CNT));
+    else asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a4[0]) : "n"(CNT));
+    if constexpr (TN == 5) asm volatile("" : "+v"(b4[0]), "+v"(b4[1]), "+v"(b4[2]), "+v"(b4[3]), "+v"(b4[4]));
+    else if constexpr (TN == 4) asm volatile("" : "+v"(b4[0]), "+v"(b4[1]), "+v"(b4[2]), "+v"(b4[3]));
+    else if constexpr (TN == 3) asm volatile("" : "+v"(b4[0]), "+v"(b4[1]), "+v"(b4[2]));
+    else if constexpr (TN == 2) asm volatile("" : "+v"(b4[0]), "+v"(b4[1]));
+    else asm volatile("" : "+v"(b4[0]));
+    __builtin_amdgcn_sched_barrier(0);  // no MFMA above the wait
+  };
+  // Row sums of dz on the matrix pipe (the layers; the heads keep their VALU sums): one 16x16x32 MFMA per A tile.  Read as a 16 x 32
+  // operand, the fragment of lane l is row l & 15 with k-group l >> 4, where the data is row (l & 15) + 16 * ((l >> 4) & 1), chunk l >> 5
+  // of the 32 x 16 tile; against B[g][j] = ((g ^ j) & 1) == 0 column 0 sums rows 0..15 and column 1 rows 16..31 over all 16 samples.
+  const unsigned one2 = (((lane & 15) ^ (lane >> 4)) & 1) == 0 ? 0x3f803f80u : 0u;
+  const u32x4_t ones4 = {one2, one2, one2, one2};
+  auto mfmas = [&](const u32x4_t (&a4)[TM], const u32x4_t (&b4)[TN]) {
+    if (do_db) {
+      if constexpr (DB_MFMA) {
+        bf16x8_t ov;
+        __builtin_memcpy(&ov, &ones4, 16);
 #pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-      // chunk 2*sub + h -> slot (2*sub + h) ^ f = slot(sub 0) ^ (2*sub): byte address ^ 32
-      const unsigned xa = oa ^ (unsigned)(32 * sub), xb = ob ^ (unsigned)(32 * sub);
-      u32x4_t a4[TM], b4[TN];
-      sfor<0, TM>([&](auto ic) { a4[decltype(ic)::value] = lds_read16<decltype(ic)::value * 2048>(xa); });
-      sfor<0, TN>([&](auto jc) { b4[decltype(jc)::value] = lds_read16<decltype(jc)::value * 2048>(xb); });
-      // the reads are asm the compiler cannot see through: tie every destination to the wait
-      if constexpr (TM == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a4[0]), "+v"(a4[1]), "+v"(a4[2]), "+v"(a4[3]));
-      else if constexpr (TM == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a4[0]), "+v"(a4[1]));
-      else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a4[0]));
-      if constexpr (TN == 5) asm volatile("" : "+v"(b4[0]), "+v"(b4[1]), "+v"(b4[2]), "+v"(b4[3]), "+v"(b4[4]));
-      else if constexpr (TN == 4) asm volatile("" : "+v"(b4[0]), "+v"(b4[1]), "+v"(b4[2]), "+v"(b4[3]));
-      else if constexpr (TN == 3) asm volatile("" : "+v"(b4[0]), "+v"(b4[1]), "+v"(b4[2]));
-      else if constexpr (TN == 2) asm volatile("" : "+v"(b4[0]), "+v"(b4[1]));
-      else asm volatile("" : "+v"(b4[0]));
-#pragma unroll
-      for (int j = 0; j < TN; ++j)  // column tiles past the end of a short B operand multiply zeros (branch-free)
-        if (!bv_[j]) b4[j] = u32x4_t{0u, 0u, 0u, 0u};
-      if (do_db) {
+        for (int i = 0; i < TM; ++i) {
+          bf16x8_t av;
+          __builtin_memcpy(&av, &a4[i], 16);
+          dbacc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, ov, dbacc[i], 0, 0, 0);
+        }
+      } else {
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           const unsigned int w[4] = {a4[i].x, a4[i].y, a4[i].z, a4[i].w};
@@ -445,39 +476,67 @@ __global__ void __launch_bounds__(64 * NW) k_mlp_wgrad_dma(const unsigned short*
           for (int q = 0; q < 4; ++q) rs[i] += bf2f((unsigned short)(w[q] & 0xffffu)) + bf2f((unsigned short)(w[q] >> 16));
         }
       }
+    }
+    // (column tiles past the end of a short B operand multiply whatever the ring holds there: their accumulators are never flushed)
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
+    for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          bf16x8_t av, bv;
-          __builtin_memcpy(&av, &a4[i], 16);
-          __builtin_memcpy(&bv, &b4[j], 16);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[i][j], 0, 0, 0);
-        }
+      for (int j = 0; j < TN; ++j) {
+        bf16x8_t av, bv;
+        __builtin_memcpy(&av, &a4[i], 16);
+        __builtin_memcpy(&bv, &b4[j], 16);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[i][j], 0, 0, 0);
+      }
+    __builtin_amdgcn_sched_barrier(0);  // the cluster stays where it is written: between the reads it hides and the next wait
+  };
+  // this wave's transfers of every stage issued so far but the last `later` ones have landed
+  auto wait_landed = [&](int later) {
+    if (later == NSTAGE - 2) wait_vmcnt<PW * (NSTAGE - 2)>();
+    else {
+      bool done = false;
+      sfor<0, NSTAGE - 2>([&](auto rc) {
+        constexpr int R = decltype(rc)::value;
+        if (!done && later == R) { wait_vmcnt<PW * R>(); done = true; }
+      });
     }
   };
+  // The loop.  Stage s sits in buffer s % NSTAGE; its two 16-sample sub-steps use two fragment sets (a0/b0, a1/b1), and every LDS read
+  // is issued one MFMA cluster ahead of its use:
+  //     read set 1 (stage s, sub 1) | wait set 0 | MFMAs sub 0 | wait set 1 -- this wave is done with buffer s
+  //     REFILL | wait: own transfers of stage s+1 landed | s_barrier -- stage s+1 is whole, everybody is done with buffer s
+  //     read set 0 (stage s+1, sub 0) | MFMAs sub 1
+  // so there is still one barrier per stage, but no read waits in front of idle MFMAs.  REFILL = stage s + NSTAGE - 1, issued BEFORE the
+  // barrier wait into the buffer of stage s-1, which every wave left before it passed the previous barrier (a wave arrives at a barrier
+  // with lgkmcnt(0)).  The other form -- refill after the barrier into the buffer just consumed, one stage more in flight -- measured
+  // 2.92-2.95 ms against 2.89-2.92 ms on the 256 x 256 layer and is not kept.  A stage is read only after its transfers were waited for
+  // (vmcnt) by every wave AND a barrier: stage s+1 at the barrier of iteration s, stage 0 at the prologue's.
   const int N = ((s_end >> 6) - (s_begin >> 6)) * 2;  // 32-sample stages
   if (N > 0) {
+    u32x4_t a0[TM], b0[TN], a1[TM], b1[TN];
 #pragma unroll
-    for (int i = 0; i < NSTAGE - 1; ++i)
+    for (int i = 0; i < AHEAD; ++i)
       if (i < N) issue(i, i);
+    wait_landed(min(AHEAD - 1, N - 1));
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    read_frags(0, IC<0>{}, a0, b0);
     int buf = 0;
     for (int s = 0; s < N; ++s) {
-      // this wave's PW transfers of stage s have landed once at most the later stages' transfers are outstanding
-      const int later = min(NSTAGE - 2, N - 1 - s);
-      if (later == NSTAGE - 2) wait_vmcnt<PW * (NSTAGE - 2)>();
-      else {
-        bool done = false;
-        sfor<0, NSTAGE - 2>([&](auto rc) {
-          constexpr int R = decltype(rc)::value;
-          if (!done && later == R) { wait_vmcnt<PW * R>(); done = true; }
-        });
+      const int prev = buf == 0 ? NSTAGE - 1 : buf - 1, next = buf + 1 == NSTAGE ? 0 : buf + 1;
+      read_frags(buf, IC<1>{}, a1, b1);
+      wait_frags(IC<TM + TN>{}, a0, b0);
+      mfmas(a0, b0);
+      wait_frags(IC<0>{}, a1, b1);
+      if (s + 1 < N) {
+        if (s + NSTAGE - 1 < N) issue(s + NSTAGE - 1, prev);
+        wait_landed(min(NSTAGE - 2, N - 2 - s));
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        read_frags(next, IC<0>{}, a0, b0);
+        __builtin_amdgcn_sched_barrier(0);
       }
-      __builtin_amdgcn_s_barrier();  // everybody's part of stage s has landed AND everybody is done reading stage s-1 ...
-      asm volatile("" ::: "memory");
-      if (s + NSTAGE - 1 < N) issue(s + NSTAGE - 1, buf == 0 ? NSTAGE - 1 : buf - 1);  // ... whose buffer this stage overwrites
-      compute(buf);
-      buf = buf + 1 == NSTAGE ? 0 : buf + 1;
+      mfmas(a1, b1);
+      buf = next;
     }
   }
 #pragma unroll
@@ -493,8 +552,18 @@ __global__ void __launch_bounds__(64 * NW) k_mlp_wgrad_dma(const unsigned short*
       }
     }
     if (do_db) {
-      const float v = rs[i] + __shfl_xor(rs[i], 32, 64);
-      if (h == 0 && 32 * (wr * TM + i) + row < wm.db_rows) atomicAdd(db + 32 * (wr * TM + i) + row, v);
+      if constexpr (DB_MFMA) {
+        if ((lane & 15) < 2) {  // column 0: rows 0..15 of the tile, column 1: rows 16..31; register r of lane l is row 4 * (l >> 4) + r
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int o = 32 * (wr * TM + i) + 16 * (lane & 15) + 4 * (lane >> 4) + r;
+            if (o < wm.db_rows) atomicAdd(db + o, dbacc[i][r]);
+          }
+        }
+      } else {
+        const float v = rs[i] + __shfl_xor(rs[i], 32, 64);
+        if (h == 0 && 32 * (wr * TM + i) + row < wm.db_rows) atomicAdd(db + 32 * (wr * TM + i) + row, v);
+      }
     }
   }
 }
