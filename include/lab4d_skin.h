@@ -74,6 +74,26 @@ int lab4d_skin_blend_backward_acc(const float* xyz, const float* art_r, const fl
  * fused path, M*B*34 + S*(2B+18) otherwise.  Host-only, no launch. */
 long long lab4d_skin_blend_backward_workspace_floats(int S, int spf, int M, int B, int has_g_se3);
 
+/* T blends of the SAME points and delta-skin logits to T different se3 tables in one launch each way (the two forward warps of a training
+ * query, nerf.py:966-973 and deformable.py:173-198): the skin weights -- bone coordinates, logits, softmax, arg-max bone -- are evaluated once
+ * and only the dual-quaternion blend, normalise and apply repeat per target.  se3_r, se3_d, out, g_out, g_se3 are HOST arrays of T device
+ * pointers, each pointing at what the single-target entry takes.  entropy and dskin do not depend on the target: one (S) tensor each, and one
+ * upstream gradient each.  Instantiated for T = 2, spf % 256 == 0, B = 25 or 18 (and, the adjoint, with the fused per-frame reductions);
+ * anything else is refused with LAB4D_EINVAL before the first launch -- call the single-target entries per target then.
+ * Forward: out[t] equals lab4d_skin_blend_forward's with table t bit for bit.  `work`: M*B*12 floats. */
+int lab4d_skin_blend_forward_multi(const float* xyz, const float* art_r, const float* art_d, const float* gauss, const float* delta_raw, int T,
+                                   const float* const* se3_r, const float* const* se3_d, int S, int spf, int M, int B, float* const* out,
+                                   float* entropy, float* dskin, float* work, void* stream);
+/* Adjoint: g_xyz (S,3) and g_raw (S,B) are written with the sum over the targets (what lab4d_skin_blend_backward for target 0 followed by
+ * lab4d_skin_blend_backward_acc for target 1 leaves, to rounding: the targets' dL/dp are summed ahead of the softmax adjoint); g_se3[t]
+ * (M,B,8) is accumulated per target (zero-fill first); g_art_r, g_art_d written and g_gauss accumulated for the sum over the targets, or NULL
+ * together.  g_ent / g_dskin may be NULL.  `work`: lab4d_skin_blend_backward_workspace_floats(S, spf, M, B, 1) floats, which must be the
+ * fused adjoint's M*B*34 (with the LAB4D_BLEND_FUSE experiment switch off this entry refuses). */
+int lab4d_skin_blend_backward_multi(const float* xyz, const float* art_r, const float* art_d, const float* gauss, const float* delta_raw, int T,
+                                    const float* const* se3_r, const float* const* se3_d, const float* const* g_out, const float* g_ent,
+                                    const float* g_dskin, int S, int spf, int M, int B, float* g_xyz, float* g_raw, float* const* g_se3,
+                                    float* g_art_r, float* g_art_d, float* g_gauss, float* work, void* stream);
+
 /* Gaussian-bone density  max_b exp(-0.5 |x - c_b|^2 / 0.01^2) * ibeta  (nnutils/deformable.py:329-356,
  * warping.py:355-387, utils/transforms.py:28-40).  centres: (B,3); ibeta: device scalar (no host sync).
  * best: (S) int32 arg-min bone (saved for

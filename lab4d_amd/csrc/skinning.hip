@@ -645,6 +645,298 @@ __global__ void __launch_bounds__(256, (FUSE ? 2 : 1)) k_blend_bwd(const float* 
   if (FUSE && cur_m >= 0) flush(cur_m);
 }
 
+// ---------------------------------------------------------------------------------------------
+// several targets off ONE skin-weight evaluation (the two forward warps of a training query: warping.skinning_warp_forward_multi)
+// ---------------------------------------------------------------------------------------------
+// What does not depend on the target's se3 table: the softmax weights, delta, the arg-max bone, logsumexp - max.  The arithmetic of
+// blend_forward, statement by statement (the forward outputs of the multi-target kernel equal the single-target kernel's bit for bit).
+constexpr int BLEND_GROUP = 5;  // bones between two scheduling fences of the multi-target kernels (see blend_target)
+template <int B>
+struct SkinWeights {
+  float p[B];       // softmax weights
+  float dl[B];      // delta = relu(raw) * 0.1
+  int anchor;
+  float lse_minus_max;
+};
+template <int B>
+__device__ __forceinline__ void skin_weights(V3 x, const float* __restrict__ affm, const float* __restrict__ raw, SkinWeights<B>& o) {
+  float skin[B];
+  float mx = -INFINITY;
+  int am = 0;
+#pragma unroll
+  for (int b = 0; b < B; ++b) {
+    const V3 c = bone_coord(ld_aff(affm + 12 * b), x);
+    const float dlt = fmaxf(raw[b], 0.f) * 0.1f;
+    o.dl[b] = dlt;
+    skin[b] = -(dot(c, c) + dlt);
+    if (skin[b] > mx) { mx = skin[b]; am = b; }
+  }
+  float sum = 0.f;
+#pragma unroll
+  for (int b = 0; b < B; ++b) { o.p[b] = expf(skin[b] - mx); sum += o.p[b]; }
+  const float isum = 1.f / sum;
+  o.anchor = am;
+  o.lse_minus_max = logf(sum);
+#pragma unroll
+  for (int b = 0; b < B; ++b) o.p[b] *= isum;
+}
+// One target: hemisphere signs against the anchor bone, the un-normalised blend and 1 / |real part| (the last loop of blend_forward; a weight
+// times -1 is the weight negated, so the results are the same bits).  Returns the signs as a mask (bit b: sign_b = -1) -- one register where
+// the single-target kernel holds B.  The bones go in groups of BLEND_GROUP behind scheduling fences: left alone, the compiler issues the
+// scalar loads of the whole table (8 floats per bone) ahead of the first use and spills most of them.
+template <int B>
+__device__ __forceinline__ unsigned blend_target(const SkinWeights<B>& w, const float* __restrict__ sr, const float* __restrict__ sd, float (&rw)[4],
+                                                 float (&dw4)[4], float& inv) {
+  const int am = w.anchor;
+  const float a0 = sr[4 * am], a1 = sr[4 * am + 1], a2 = sr[4 * am + 2], a3 = sr[4 * am + 3];
+  unsigned neg = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { rw[k] = 0.f; dw4[k] = 0.f; }
+#pragma unroll
+  for (int b = 0; b < B; ++b) {
+    if (b % BLEND_GROUP == 0) __builtin_amdgcn_sched_barrier(0);
+    const float* r = sr + 4 * b;
+    const float* d = sd + 4 * b;
+    const bool pos = (a0 * r[0] + a1 * r[1] + a2 * r[2] + a3 * r[3]) > 0.f;  // geom_utils.py:66-70
+    neg |= (pos ? 0u : 1u) << b;
+    const float c = pos ? w.p[b] : -w.p[b];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { rw[k] += c * r[k]; dw4[k] += c * d[k]; }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  inv = 1.f / sqrtf(rw[0] * rw[0] + rw[1] * rw[1] + rw[2] * rw[2] + rw[3] * rw[3]);
+  return neg;
+}
+
+// The multi-target kernels take their per-target pointers as individual __restrict__ kernel parameters, written out for two targets: that
+// qualifier on a kernel parameter is what lets the compiler fetch the frame's se3 table with scalar loads (a pointer array passed by value
+// loses it, and the 200 table floats then arrive through per-lane loads into vector registers).  pick() selects target t's pointer with a
+// compare (the target loops are unrolled: it folds to the parameter).
+template <typename P>
+__device__ __forceinline__ P pick(int t, P a0, P a1) { return t == 0 ? a0 : a1; }
+
+// k_blend_fwd<B, true> for T targets: raw, xyz and the skin weights once, then blend / normalise / apply per target.  entropy and delta_skin
+// do not depend on the target and are written once.
+template <int B, int T>
+__global__ void __launch_bounds__(256) k_blend_fwd_multi(const float* __restrict__ xyz, const float* __restrict__ aff, const float* __restrict__ raw,
+                                                          const float* __restrict__ sr0, const float* __restrict__ sd0, const float* __restrict__ sr1,
+                                                          const float* __restrict__ sd1, long S, int spf, float* __restrict__ out0,
+                                                          float* __restrict__ out1, float* __restrict__ ent, float* __restrict__ dskin) {
+  static_assert(T == 2, "the per-target pointer parameters are written out for two targets");
+  using R = RowTile<B>;
+  __shared__ float tile[R::FLOATS];
+  for (long s0 = (long)blockIdx.x * 256; s0 < S; s0 += (long)gridDim.x * 256) {
+    const long rem = S - s0;
+    const int n = (int)(rem < 256 ? rem : 256);
+    R::load(raw, s0, n, tile);
+    __syncthreads();
+    if ((int)threadIdx.x < n) {
+      const long s = s0 + threadIdx.x;
+      const int m = __builtin_amdgcn_readfirstlane(frame_of(s0, spf));
+      const V3 x = ldv3(xyz + s * 3);
+      SkinWeights<B> w;
+      skin_weights<B>(x, aff + (size_t)m * B * 12, tile + threadIdx.x * R::CP, w);
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        float rw[4], dw4[4], i;
+        blend_target<B>(w, pick(t, sr0, sr1) + (size_t)m * B * 4, pick(t, sd0, sd1) + (size_t)m * B * 4, rw, dw4, i);
+        const V3 y = dq_apply(rw[0] * i, V3{rw[1], rw[2], rw[3]} * i, dw4[0] * i, V3{dw4[1], dw4[2], dw4[3]} * i, x);
+        stv3(pick(t, out0, out1) + s * 3, y);
+      }
+      if (ent) ent[s] = w.lse_minus_max;
+      if (dskin) {
+        float q = 0.f;
+#pragma unroll
+        for (int b = 0; b < B; ++b) q += w.dl[b] * w.dl[b];
+        dskin[s] = q / (float)B;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// k_blend_bwd<B, true, true> for T targets whose adjoints land in ONE g_xyz / g_raw pair.  Per target: the blend with that target's table, the
+// adjoint of normalise + apply, its [g_rw | g_dw] row and its g_se3[t][m] += coef^T gw reduction; dL/dp_b is summed over the targets in
+// registers.  Once, on that sum: the softmax / entropy / delta adjoint, gsk, the push of gsk_b c_b to the point, g_raw, and the second-moment
+// reduction Q[m] += gsk^T xx (linear in gsk).  The sum over the targets is taken BEFORE the softmax adjoint, where the single-target kernel
+// run once per target (the second time with ACC) adds the two finished g_xyz / g_raw: equal to rounding, not bit for bit.
+template <int B, int T>
+__global__ void __launch_bounds__(256, 2) k_blend_bwd_multi(const float* __restrict__ xyz, const float* __restrict__ aff, const float* __restrict__ raw,
+                                                             const float* __restrict__ sr0, const float* __restrict__ sd0, const float* __restrict__ sr1,
+                                                             const float* __restrict__ sd1, const float* __restrict__ g_out0,
+                                                             const float* __restrict__ g_out1, const float* __restrict__ g_ent,
+                                                             const float* __restrict__ g_dskin, long S, int spf, float* __restrict__ g_xyz,
+                                                             float* __restrict__ g_raw, float* __restrict__ g_se3_0, float* __restrict__ g_se3_1,
+                                                             float* __restrict__ Qm) {
+  static_assert(T == 2, "the per-target pointer parameters are written out for two targets");
+  using R = RowTile<B>;
+  __shared__ float tile[R::FLOATS];
+  constexpr int AUXW = 12;
+  constexpr int SLICES = 256 / B;
+  constexpr int NSE3 = T * B * 8;          // block sums: [T x B x 8 | B x 10]
+  static_assert(R::FLOATS >= SLICES * B * 10, "the tile doubles as the slice-reduction scratch");
+  __shared__ __attribute__((aligned(16))) float aux[256 * AUXW];
+  __shared__ float lacc[NSE3 + B * 10];
+  // the raw rows stay in a tile of their own until g_raw is formed (delta and the ReLU mask are read off them there): held in registers
+  // across the target loop they were 26 more than two waves per SIMD leave room for
+  __shared__ float keep[R::FLOATS];
+  int cur_m = -1;
+  for (int e = threadIdx.x; e < NSE3 + B * 10; e += 256) lacc[e] = 0.f;  // (the first __syncthreads of the loop orders this against the first use)
+  auto flush = [&](int m) {  // block sums -> the per-frame accumulators; callers sync before and after
+    for (int e = threadIdx.x; e < NSE3 + B * 10; e += 256) {
+      const float v = lacc[e];
+      if (v != 0.f) {
+        if (e < NSE3) { const int t = e / (B * 8); atomicAdd(pick(t, g_se3_0, g_se3_1) + (size_t)m * B * 8 + (e - t * B * 8), v); }
+        else atomicAdd(Qm + (size_t)m * B * 10 + (e - NSE3), v);
+      }
+      lacc[e] = 0.f;
+    }
+  };
+  // acc[j] = sum over the rows k = sl, sl + SLICES, ... < n of tile[k][i] * aux[k][j]; then the slices are summed through the tile (k_blend_bwd)
+  auto gram = [&](int n, int ncol, int off) {
+    const int t = threadIdx.x, sl = t / B, i = t - sl * B;
+    const bool act = sl < SLICES;
+    float acc[10];
+#pragma unroll
+    for (int j = 0; j < 10; ++j) acc[j] = 0.f;
+    if (act)
+      for (int k = sl; k < n; k += SLICES) {
+        const float a = tile[k * R::CP + i];
+        const float4 b0 = *reinterpret_cast<const float4*>(aux + k * AUXW), b1 = *reinterpret_cast<const float4*>(aux + k * AUXW + 4);
+        acc[0] += a * b0.x; acc[1] += a * b0.y; acc[2] += a * b0.z; acc[3] += a * b0.w;
+        acc[4] += a * b1.x; acc[5] += a * b1.y; acc[6] += a * b1.z; acc[7] += a * b1.w;
+        if (ncol == 10) {
+          const float2 b2 = *reinterpret_cast<const float2*>(aux + k * AUXW + 8);
+          acc[8] += a * b2.x; acc[9] += a * b2.y;
+        }
+      }
+    __syncthreads();
+    if (act)
+      for (int j = 0; j < ncol; ++j) tile[(sl * B + i) * ncol + j] = acc[j];
+    __syncthreads();
+    for (int e = t; e < B * ncol; e += 256) {
+      float v = 0.f;
+#pragma unroll
+      for (int q = 0; q < SLICES; ++q) v += tile[q * B * ncol + e];
+      lacc[off + e] += v;
+    }
+    __syncthreads();
+  };
+  for (long s0 = (long)blockIdx.x * 256; s0 < S; s0 += (long)gridDim.x * 256) {
+    const long rem = S - s0;
+    const int n = (int)(rem < 256 ? rem : 256);
+    const bool active = (int)threadIdx.x < n;
+    const long s = s0 + threadIdx.x;
+    float* row = tile + threadIdx.x * R::CP;
+    const int m = __builtin_amdgcn_readfirstlane(frame_of(s0, spf));
+    if (m != cur_m) {  // block-uniform
+      if (cur_m >= 0) { __syncthreads(); flush(cur_m); }
+      cur_m = m;
+    }
+    R::load(raw, s0, n, keep);
+    __syncthreads();
+    const float* rawrow = keep + threadIdx.x * R::CP;
+    SkinWeights<B> w;
+    float gp[B];      // dL/dp_b, summed over the targets
+    const float* affm = aff + (size_t)m * B * 12;
+    V3 x = {0, 0, 0}, gx = {0, 0, 0};
+    if (active) {
+      x = ldv3(xyz + s * 3);
+      skin_weights<B>(x, affm, rawrow, w);
+#pragma unroll
+      for (int b_ = 0; b_ < B; ++b_) gp[b_] = 0.f;
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const float* srm = pick(t, sr0, sr1) + (size_t)m * B * 4;
+      const float* sdm = pick(t, sd0, sd1) + (size_t)m * B * 4;
+      // the adjoint's second pass over the table fetches it again, group by group, through an offset the compiler cannot see through: held
+      // over from the blend it would be 200 live scalars
+      int zero = 0;
+      asm volatile("" : "+v"(zero));
+      const int again = m * B * 4 + __builtin_amdgcn_readfirstlane(zero);
+      if (active) {
+        const V3 g = ldv3(pick(t, g_out0, g_out1) + s * 3);
+        float rw[4], dw4[4], i;
+        const unsigned neg = blend_target<B>(w, srm, sdm, rw, dw4, i);
+        const float qw = rw[0] * i, dw = dw4[0] * i;
+        const V3 v = V3{rw[1], rw[2], rw[3]} * i, dv = V3{dw4[1], dw4[2], dw4[3]} * i;
+        gx = gx + qrot_t(qw, v, g);
+        float gqw; V3 gqv;
+        qrot_gq(qw, v, x, g, gqw, gqv);
+        // t = 2 (-dw v + w dv + v x dv)
+        const float gn_w = gqw + 2.f * dot(dv, g);
+        const V3 gn_v = gqv + g * (-2.f * dw) + cross(dv, g) * 2.f;
+        const float gd_w = -2.f * dot(v, g);
+        const V3 gd_v = g * (2.f * qw) + cross(g, v) * 2.f;
+        // normalisation: qn = rw * inv, dn = dw4 * inv, inv = 1/|rw|
+        const float qg = qw * gn_w + dot(v, gn_v);
+        const float dg = dw * gd_w + dot(dv, gd_v);
+        float grw[4], gdw[4];
+        grw[0] = i * (gn_w - qw * qg) - qw * i * dg;
+        grw[1] = i * (gn_v.x - v.x * qg) - v.x * i * dg;
+        grw[2] = i * (gn_v.y - v.y * qg) - v.y * i * dg;
+        grw[3] = i * (gn_v.z - v.z * qg) - v.z * i * dg;
+        gdw[0] = i * gd_w; gdw[1] = i * gd_v.x; gdw[2] = i * gd_v.y; gdw[3] = i * gd_v.z;
+        float4* wg = reinterpret_cast<float4*>(aux + threadIdx.x * AUXW);
+        wg[0] = make_float4(grw[0], grw[1], grw[2], grw[3]);
+        wg[1] = make_float4(gdw[0], gdw[1], gdw[2], gdw[3]);
+#pragma unroll
+        for (int b_ = 0; b_ < B; ++b_) {
+          if (b_ % BLEND_GROUP == 0) __builtin_amdgcn_sched_barrier(0);
+          const float* r = pick(t, sr0, sr1) + again + 4 * b_;
+          const float* d = pick(t, sd0, sd1) + again + 4 * b_;
+          const float gpb = r[0] * grw[0] + r[1] * grw[1] + r[2] * grw[2] + r[3] * grw[3] + d[0] * gdw[0] + d[1] * gdw[1] + d[2] * gdw[2] + d[3] * gdw[3];
+          const bool ng = (neg >> b_) & 1u;
+          gp[b_] += ng ? -gpb : gpb;
+          row[b_] = ng ? -w.p[b_] : w.p[b_];  // coef[s][b] = p_b * sign_b
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __syncthreads();
+      gram(n, 8, t * B * 8);  // g_se3[t] += coef^T gw   (ends with a barrier)
+    }
+    float pg = 0.f, ge = 0.f, gds = 0.f;
+    if (active) {
+#pragma unroll
+      for (int b_ = 0; b_ < B; ++b_) pg += w.p[b_] * gp[b_];
+      ge = g_ent ? g_ent[s] : 0.f;
+      gds = g_dskin ? g_dskin[s] * (2.f / (float)B) : 0.f;
+      // dL/dx through c_b = Abar_b [x,1]:  Abar_b[:, :3]^T (gsk * c_b)
+#pragma unroll
+      for (int b_ = 0; b_ < B; ++b_) {
+        const float gskin = w.p[b_] * (gp[b_] - pg) + ge * (w.p[b_] - (b_ == w.anchor ? 1.f : 0.f));
+        const float gsk = -2.f * gskin;
+        const Aff A = ld_aff(affm + 12 * b_);
+        const V3 c = bone_coord(A, x);
+        const float u0 = gsk * c.x, u1 = gsk * c.y, u2 = gsk * c.z;
+        gx = gx + V3{A.r0.x * u0 + A.r1.x * u1 + A.r2.x * u2, A.r0.y * u0 + A.r1.y * u1 + A.r2.y * u2, A.r0.z * u0 + A.r1.z * u1 + A.r2.z * u2};
+        row[b_] = gsk;  // gsk[s][b]
+      }
+      stv3(g_xyz + s * 3, gx);
+      float* xx = aux + threadIdx.x * AUXW;  // upper triangle of [x,1][x,1]^T, row-major: the second operand of Q += gsk^T xx
+      xx[0] = x.x * x.x; xx[1] = x.x * x.y; xx[2] = x.x * x.z; xx[3] = x.x;
+      xx[4] = x.y * x.y; xx[5] = x.y * x.z; xx[6] = x.y;
+      xx[7] = x.z * x.z; xx[8] = x.z; xx[9] = 1.f;
+    }
+    __syncthreads();
+    gram(n, 10, NSE3);
+    if (active) {
+#pragma unroll
+      for (int b_ = 0; b_ < B; ++b_) {
+        const float gskin = w.p[b_] * (gp[b_] - pg) + ge * (w.p[b_] - (b_ == w.anchor ? 1.f : 0.f));
+        const float rb = rawrow[b_];
+        const float gdelta = -gskin + gds * (fmaxf(rb, 0.f) * 0.1f);
+        row[b_] = rb > 0.f ? 0.1f * gdelta : 0.f;  // the ReLU of the delta-skin head, skinning.py:119
+      }
+    }
+    __syncthreads();
+    R::store(g_raw, s0, n, tile);
+    __syncthreads();
+  }
+  if (cur_m >= 0) flush(cur_m);
+}
+
 // Gram matrix of the blend's bone-coordinate path from its per-frame second moments (see k_blend_bwd):
 //   G[m,b,k,j] = sum_s gsk_sb c_sbk [x_s,1]_j = (1/gauss_bk) sum_i A_b[k][i] Q_b[i][j],  A_b = [R_b | t_b],  Q_b symmetric 4x4.
 // One thread per (m,b); G (M,B,3,4) is written.
@@ -903,6 +1195,57 @@ extern "C" int lab4d_skin_blend_backward_acc(const float* xyz, const float* art_
     // bone-coordinate path: per-frame moments -> Gram matrix -> (M,B)-sized chain rule
     if (!fused)
       if (int e = lab4d_gram_per_frame(ws + (size_t)S * (B + 8), B, ws + (size_t)S * (2 * B + 8), 10, S, spf, M, Q, stream)) return e;
+    hipLaunchKernelGGL(k_bone_gram_from_moments, dim3(div_up(M * B, 64)), dim3(64), 0, st, art_r, art_d, gauss, Q, M, B, G);
+    if (int e = check_launch("bone_gram_from_moments")) return e;
+    return lab4d_bone_params_from_gram(art_r, art_d, gauss, G, M, B, g_art_r, g_art_d, g_gauss, stream);
+  }
+  return LAB4D_OK;
+}
+
+// The multi-target entries take exactly what their kernels are instantiated for: T = 2 targets, frame-uniform tiles, B = 25 / 18, and for the
+// adjoint the fused per-frame reductions.  Everything else is the caller's per-target loop over the single-target entries.
+#define SKIN_MULTI_T 2
+static bool blend_multi_shape(int T, int spf, int B) { return T == SKIN_MULTI_T && spf > 0 && spf % 256 == 0 && (B == 25 || B == 18); }
+#define SKIN_MULTI_REQUIRE(WHAT, T, spf, B)                                                                                                     \
+  LAB4D_REQUIRE(blend_multi_shape(T, spf, B), WHAT ": instantiated for T = 2 targets, spf %% 256 == 0 and B = 25 or 18; got T=%d spf=%d B=%d " \
+                "(use the single-target entry per target)", T, spf, B)
+
+extern "C" int lab4d_skin_blend_forward_multi(const float* xyz, const float* art_r, const float* art_d, const float* gauss, const float* raw, int T,
+                                              const float* const* sr, const float* const* sd, int S, int spf, int M, int B, float* const* out,
+                                              float* ent, float* dskin, float* work, void* stream) {
+  LAB4D_REQUIRE(xyz && art_r && art_d && gauss && raw && sr && sd && out && work, "skin_blend_forward_multi: null pointer");
+  SKIN_MULTI_REQUIRE("skin_blend_forward_multi", T, spf, B);
+  LAB4D_REQUIRE((long)M * spf >= S, "skin_blend_forward_multi: M*spf < S");
+  for (int t = 0; t < SKIN_MULTI_T; ++t) LAB4D_REQUIRE(sr[t] && sd[t] && out[t], "skin_blend_forward_multi: null pointer (target %d)", t);
+  if (S == 0) return LAB4D_OK;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_bone_affine, dim3(div_up(M * B, 64)), dim3(64), 0, st, art_r, art_d, gauss, M, B, work);
+  SKIN_DISPATCH(B, hipLaunchKernelGGL((k_blend_fwd_multi<NB, SKIN_MULTI_T>), dim3(grid_1d(S, 256, 8192)), dim3(256), 0, st, xyz, work, raw, sr[0], sd[0], sr[1], sd[1], (long)S, spf, out[0], out[1], ent, dskin));
+  return check_launch("skin_blend_forward_multi");
+}
+
+extern "C" int lab4d_skin_blend_backward_multi(const float* xyz, const float* art_r, const float* art_d, const float* gauss, const float* raw, int T,
+                                               const float* const* sr, const float* const* sd, const float* const* g_out, const float* g_ent,
+                                               const float* g_dskin, int S, int spf, int M, int B, float* g_xyz, float* g_raw, float* const* g_se3,
+                                               float* g_art_r, float* g_art_d, float* g_gauss, float* work, void* stream) {
+  LAB4D_REQUIRE(xyz && art_r && art_d && gauss && raw && sr && sd && g_out && g_xyz && g_raw && g_se3 && work, "skin_blend_backward_multi: null pointer");
+  SKIN_MULTI_REQUIRE("skin_blend_backward_multi", T, spf, B);
+  LAB4D_REQUIRE(blend_bwd_fused(spf, true), "skin_blend_backward_multi: needs the fused adjoint (LAB4D_BLEND_FUSE=0 is set)");
+  LAB4D_REQUIRE((long)M * spf >= S, "skin_blend_backward_multi: M*spf < S");
+  for (int t = 0; t < SKIN_MULTI_T; ++t) LAB4D_REQUIRE(sr[t] && sd[t] && g_out[t] && g_se3[t], "skin_blend_backward_multi: null pointer (target %d)", t);
+  if (S == 0) return LAB4D_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // work = [aff (M,B,12) | Q (M,B,10) | G (M,B,12)], as in lab4d_skin_blend_backward_acc
+  float* aff = work;
+  float* Q = work + (size_t)M * B * 12;
+  float* G = Q + (size_t)M * B * 10;
+  const bool params = g_art_r || g_art_d || g_gauss;
+  hipLaunchKernelGGL(k_bone_affine, dim3(div_up(M * B, 64)), dim3(64), 0, st, art_r, art_d, gauss, M, B, aff);
+  if (int e = zero_async(Q, (size_t)M * B * 10 * sizeof(float), st)) return e;
+  const int grid = grid_1d(S, 256, 2048);  // resident blocks, as the fused single-target adjoint
+  SKIN_DISPATCH(B, hipLaunchKernelGGL((k_blend_bwd_multi<NB, SKIN_MULTI_T>), dim3(grid), dim3(256), 0, st, xyz, aff, raw, sr[0], sd[0], sr[1], sd[1], g_out[0], g_out[1], g_ent, g_dskin, (long)S, spf, g_xyz, g_raw, g_se3[0], g_se3[1], Q));
+  if (int e = check_launch("skin_blend_backward_multi")) return e;
+  if (params) {
     hipLaunchKernelGGL(k_bone_gram_from_moments, dim3(div_up(M * B, 64)), dim3(64), 0, st, art_r, art_d, gauss, Q, M, B, G);
     if (int e = check_launch("bone_gram_from_moments")) return e;
     return lab4d_bone_params_from_gram(art_r, art_d, gauss, G, M, B, g_art_r, g_art_d, g_gauss, stream);

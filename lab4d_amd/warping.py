@@ -1,6 +1,7 @@
 """Host-side mirror of lab4d/nnutils/warping.py SkinningWarp.forward (+ skinning.py SkinningField,
 transforms.get_bone_coords, geom_utils.dual_quaternion_skinning, loss_utils.cross_entropy_skin_loss)
 on the gfx950 kernels of csrc/skinning.hip and the fused delta-skin MLP (LAB4D_NET_SKIN)."""
+import ctypes
 import os
 
 import torch
@@ -218,12 +219,39 @@ class SkinBlend(Function):
         return gx, gr, gar, gad, gg, gse3[..., :4].contiguous(), gse3[..., 4:].contiguous(), None
 
 
+# The two forward warps of a training query share one blend launch each way (lab4d_skin_blend_*_multi: the skin weights are evaluated once,
+# only the dual-quaternion blend repeats per target); 0 restores one launch per target (A/B measurements, tests/test_gpu_skinning_multi.py).
+SKIN_BLEND_MULTI = os.environ.get("LAB4D_SKIN_BLEND_MULTI", "1") != "0"
+
+
+def _blend_multi_shape(spf, B, T):
+    """Whether the library's multi-target entries take this shape: they are instantiated for two targets, spf % 256 == 0 and B in {18, 25}
+    (include/lab4d_skin.h)."""
+    return SKIN_BLEND_MULTI and T == 2 and spf % 256 == 0 and B in (18, 25)
+
+
+def _blend_multi_work(S, spf, M, B, T, device):
+    """Scratch of the multi-target adjoint, or None where it does not run: outside _blend_multi_shape, or with the unfused per-frame reductions
+    (LAB4D_BLEND_FUSE=0; the forward has no such condition)."""
+    if not _blend_multi_shape(spf, B, T):
+        return None
+    work, fused = _blend_bwd_work(S, spf, M, B, device)
+    return work if fused else None
+
+
+def _pointers(tensors):
+    """A host array of device pointers (the `const float* const*` parameters of the multi-target entries)."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
 class SkinBlendMulti(Function):
     """Several blends (SkinBlend) of the SAME points and delta-skin logits to different target transforms -- the two forward warps of a training
-    query (skinning_warp_forward_multi).  Forward: SkinBlend's kernel once per target.  Backward: the adjoints of all targets land in ONE
-    (S,3) / (S,B) pair (lab4d_skin_blend_backward_acc: the second and later launches add), where autograd would sum two (S,B) tensors in a
-    pass of its own (5 GB of traffic per chunk at B = 25).  Arguments: xyz, raw, art_r, art_d, gauss, spf, then (se3_r, se3_d) per target;
-    returns (out, entropy, delta_skin) per target, flattened."""
+    query (skinning_warp_forward_multi).  entropy and delta_skin depend on the skin weights alone, so they are returned ONCE.  Where the library
+    has a multi-target kernel for the shape (two targets, spf % 256 == 0, B = 18 / 25) each direction is one launch that evaluates the skin
+    weights once; otherwise SkinBlend's kernel runs once per target, and in the backward the adjoints of all targets land in ONE (S,3) / (S,B)
+    pair (lab4d_skin_blend_backward_acc: the second and later launches add), where autograd would sum two (S,B) tensors in a pass of its own
+    (5 GB of traffic per chunk at B = 25).  Arguments: xyz, raw, art_r, art_d, gauss, spf, then (se3_r, se3_d) per target; returns
+    (out per target ..., entropy, delta_skin)."""
 
     @staticmethod
     def forward(ctx, xyz, raw, art_r, art_d, gauss, spf, *se3s):
@@ -231,54 +259,68 @@ class SkinBlendMulti(Function):
         se3s = [t.contiguous() for t in se3s]
         _lib.require_device(xyz, raw, art_r, art_d, gauss, *se3s)
         S, (M, B) = xyz.shape[0], art_r.shape[:2]
-        outs = []
-        for i in range(0, len(se3s), 2):
-            out = torch.empty(S, 3, device=xyz.device)
-            ent = torch.empty(S, 1, device=xyz.device)
-            dsk = torch.empty(S, 1, device=xyz.device)
-            work = torch.empty(M * B * 12, device=xyz.device)
-            with _lib.timed("k_blend_fwd", (0.0, 4.0 * S * (3 + B + 3 + 2))):
-                _lib.call("skin_blend_forward", xyz, art_r, art_d, gauss, raw, se3s[i], se3s[i + 1], S, spf, M, B, out, ent, dsk, work)
-            outs += [out, ent, dsk]
+        T = len(se3s) // 2
+        outs = [torch.empty(S, 3, device=xyz.device) for _ in range(T)]
+        ent = torch.empty(S, 1, device=xyz.device)
+        dsk = torch.empty(S, 1, device=xyz.device)
+        work = torch.empty(M * B * 12, device=xyz.device)
+        if _blend_multi_shape(spf, B, T):
+            with _lib.timed("k_blend_fwd_multi", (0.0, 4.0 * S * (3 + B + 3 * T + 2))):  # xyz + raw read once; T outs, entropy, delta_skin written
+                _lib.call("skin_blend_forward_multi", xyz, art_r, art_d, gauss, raw, T, _pointers(se3s[0::2]), _pointers(se3s[1::2]), S, spf, M, B,
+                          _pointers(outs), ent, dsk, work)
+        else:
+            for i in range(T):  # entropy and delta_skin: written by the first launch only
+                with _lib.timed("k_blend_fwd", (0.0, 4.0 * S * (3 + B + 3 + (2 if i == 0 else 0)))):
+                    _lib.call("skin_blend_forward", xyz, art_r, art_d, gauss, raw, se3s[2 * i], se3s[2 * i + 1], S, spf, M, B, outs[i],
+                              ent if i == 0 else None, dsk if i == 0 else None, work)
         ctx.save_for_backward(xyz, raw, art_r, art_d, gauss, *se3s)
         ctx.spf = spf
-        return tuple(outs)
+        return tuple(outs) + (ent, dsk)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
         xyz, raw, art_r, art_d, gauss, *se3s = ctx.saved_tensors
         S, (M, B) = xyz.shape[0], art_r.shape[:2]
+        T = len(se3s) // 2
+        g_outs, (g_ent, g_dsk) = list(grads[:T]), grads[T:]
+        if all(g is None for g in grads):
+            return (None,) * (6 + len(se3s))
+        g_ent = g_ent.contiguous() if g_ent is not None else None
+        g_dsk = g_dsk.contiguous() if g_dsk is not None else None
+        live = [i for i in range(T) if g_outs[i] is not None] or [0]   # (entropy / delta_skin alone: they ride on target 0, with a zero cotangent)
+        g_outs = [torch.zeros_like(xyz) if (g is None and i in live) else (g.contiguous() if g is not None else None) for i, g in enumerate(g_outs)]
         gx, gr = torch.empty_like(xyz), torch.empty_like(raw)
         need_p = any(ctx.needs_input_grad[2:5])
-        # (the fused / unfused decision is a function of S -- with S = 0 both paths size their scratch M*B*34 -- so it is asked for the
-        # real S, and that (work, fused) pair serves the first target instead of being thrown away)
-        work0, fused = _blend_bwd_work(S, ctx.spf, M, B, xyz.device)
-        gar = gad = gg = None
+        gse3 = {i: torch.zeros(M, B, 8, device=xyz.device) for i in live}
+        work = _blend_multi_work(S, ctx.spf, M, B, T, xyz.device) if len(live) == T else None
+        if work is not None:
+            gar = torch.empty_like(art_r) if need_p else None
+            gad = torch.empty_like(art_d) if need_p else None
+            gg = torch.zeros_like(gauss) if need_p else None
+            # reads xyz, raw, T cotangents, g_ent, g_dskin once; writes g_xyz, g_raw once
+            with _lib.timed("k_blend_bwd_multi+gram", (0.0, 4.0 * S * ((3 + B + 3 * T + 2) + (3 + B)))):
+                _lib.call("skin_blend_backward_multi", xyz, art_r, art_d, gauss, raw, T, _pointers(se3s[0::2]), _pointers(se3s[1::2]), _pointers(g_outs),
+                          g_ent, g_dsk, S, ctx.spf, M, B, gx, gr, _pointers([gse3[i] for i in range(T)]), gar, gad, gg, work)
+        else:
+            # (the fused / unfused decision is a function of S -- with S = 0 both paths size their scratch M*B*34 -- so it is asked for
+            # the real S)
+            gar = gad = gg = None
+            for k, i in enumerate(live):
+                first, last = k == 0, k == len(live) - 1
+                work, fused = _blend_bwd_work(S, ctx.spf, M, B, xyz.device)
+                par = torch.empty_like(art_r) if need_p else None
+                pad = torch.empty_like(art_d) if need_p else None
+                pg = torch.zeros_like(gauss) if need_p else None
+                with _lib.timed("k_blend_bwd+gram", (0.0, 4.0 * S * ((3 + B + 3 + 2) + (3 + B) * (1 if first else 2) + (0 if fused else 2 * (2 * B + 18))))):
+                    # the cotangents of the shared entropy / delta_skin go in with the last target (the adjoint is linear in them)
+                    _lib.call("skin_blend_backward_acc", xyz, art_r, art_d, gauss, raw, se3s[2 * i], se3s[2 * i + 1], g_outs[i], g_ent if last else None,
+                              g_dsk if last else None, S, ctx.spf, M, B, gx, gr, gse3[i], par, pad, pg, work, 0 if first else 1)
+                if need_p:  # (M,B)-sized: summed over the targets here
+                    gar, gad, gg = (par, pad, pg) if gar is None else (gar + par, gad + pad, gg + pg)
         gse3s = []
-        first = True
-        for i in range(0, len(se3s), 2):
-            g_out, g_ent, g_dsk = grads[3 * (i // 2):3 * (i // 2) + 3]
-            if g_out is None and g_ent is None and g_dsk is None:
-                gse3s += [None, None]
-                continue
-            g_out = torch.zeros_like(xyz) if g_out is None else g_out.contiguous()
-            g_ent = g_ent.contiguous() if g_ent is not None else None
-            g_dsk = g_dsk.contiguous() if g_dsk is not None else None
-            gse3 = torch.zeros(M, B, 8, device=xyz.device)
-            par = torch.empty_like(art_r) if need_p else None
-            pad = torch.empty_like(art_d) if need_p else None
-            pg = torch.zeros_like(gauss) if need_p else None
-            work = work0 if first else _blend_bwd_work(S, ctx.spf, M, B, xyz.device)[0]
-            with _lib.timed("k_blend_bwd+gram", (0.0, 4.0 * S * ((3 + B + 3 + 2) + (3 + B) * (1 if first else 2) + (0 if fused else 2 * (2 * B + 18))))):
-                _lib.call("skin_blend_backward_acc", xyz, art_r, art_d, gauss, raw, se3s[i], se3s[i + 1], g_out, g_ent, g_dsk, S, ctx.spf, M, B, gx, gr, gse3,
-                          par, pad, pg, work, 0 if first else 1)
-            first = False
-            if need_p:  # (M,B)-sized: summed over the targets here
-                gar, gad, gg = (par, pad, pg) if gar is None else (gar + par, gad + pad, gg + pg)
-            gse3s += [gse3[..., :4].contiguous(), gse3[..., 4:].contiguous()]
-        if first:
-            return (None,) * (6 + len(se3s))
+        for i in range(T):
+            gse3s += [gse3[i][..., :4].contiguous(), gse3[i][..., 4:].contiguous()] if i in gse3 else [None, None]
         return (gx, gr, gar, gad, gg, None) + tuple(gse3s)
 
 
@@ -370,11 +412,8 @@ def skinning_warp_forward_multi(P, xyz, t_articulations, rest_articulation, t_em
     rest_inv = None if pre is not None else Q.dual_quaternion_inverse(rest_articulation)
     se3s = [pre["se3s"][i] if pre is not None else Q.dual_quaternion_mul(t_art, rest_inv) for i, t_art in enumerate(t_articulations)]
     flat = SkinBlendMulti.apply(x, raw, rest_articulation[0], rest_articulation[1], gauss, spf, *[t for se3 in se3s for t in se3])
-    outs = []
-    for i in range(len(se3s)):
-        out, ent, dsk = flat[3 * i:3 * i + 3]
-        outs.append((out.view(shape), {"skin_entropy": ent.view(shape[:-1] + (1,)), "delta_skin": dsk.view(shape[:-1] + (1,))}))
-    return outs
+    ent, dsk = flat[len(se3s):]  # the skin weights' terms: the same for every target
+    return [(out.view(shape), {"skin_entropy": ent.view(shape[:-1] + (1,)), "delta_skin": dsk.view(shape[:-1] + (1,))}) for out in flat[:len(se3s)]]
 
 
 def dense_warp(P, xyz, t_embed, code, backward, prec=mlp.PREC_F32, prefix="warp.post_warp.", net=mlp.NET_DENSE):
