@@ -302,6 +302,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_distort.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 18. Sphere tracing of the hash field's SDF to one surface hit per ray (not in the reference, parity unpinned).
+ *     See lab4d_hashtrace.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_hashtrace.h"
+
 #ifdef __cplusplus
 }
 #endif

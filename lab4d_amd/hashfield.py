@@ -23,13 +23,18 @@ is opt-in.
 The SDF as an SDF: sdf_gradient() returns the sdf with its gradient in the point from one fused kernel (hashsdf.py, include/lab4d_hashsdf.h),
 differentiable in the table and the geometry net; eikonal_loss() and normals() build on it (the counterparts of nnutils/nerf.py:416-493), and
 render_packed(with_normal=True) composites a normal map.  Opt-in as well.
+
+The surface without volume rendering: trace_surface() sphere-traces the SDF to one hit per ray (hashtrace.py, include/lab4d_hashtrace.h), and
+render_surface() evaluates colour and normal once per ray at that hit -- a preview / eval path, a depth or normal map without a mesh, surface
+points for eikonal_loss() and normals().  Opt-in as well.
 """
+import collections
 import math
 
 import torch
 import torch.nn.functional as F
 
-from . import hashgrid, hashsdf, mlp, packed
+from . import hashgrid, hashsdf, hashtrace, mlp, packed
 from . import render_utils as RU
 from .deformable import volsdf_density
 
@@ -235,3 +240,60 @@ def render_packed_pruned(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.P
     if with_normal:
         out += (rendered["normal"],)
     return out + (_packed_distortion(dens_s, kept, dt),) if with_distortion else out
+
+
+Surface = collections.namedtuple("Surface", "t status n_eval sdf xyz hit")
+
+
+@torch.no_grad()
+def trace_surface(P, cfg, origin, dir, t_range, grid=None, eps=1e-4, step_scale=1.0, min_step=None, max_steps=128, n_bisect=8, res=None):
+    """Sphere-traces the field's SDF along the rays origin + t dir, t in t_range (origin, dir (R,3) in the field's frame, dir of any length,
+    t_range (R,2)), to one hit per ray (include/lab4d_hashtrace.h; ONE kernel, csrc/hashtrace.hip): steps of max(step_scale * sdf, min_step) / |dir|
+    (min_step defaults to eps) until |sdf| <= eps, a bisection of at most n_bisect evaluations where the sign changes, at most max_steps steps.
+    Returns Surface(t (R,), status (R,) int32 -- hashtrace.MISS / CONVERGED / BRACKETED / STARTS_INSIDE / OUT_OF_STEPS --, n_eval (R,) int32,
+    sdf (R,) at the hit, xyz (R,3) = origin + t dir, hit (R,) bool = status 1, 2 or 3).
+    grid: an occgrid.OccupancyGrid over P["aabb"] (optional): grid.ray_span narrows t_range to the ray's first .. last occupied cell first; a
+    ray that the span misses is traced with an empty range and gets status MISS with t = its own t0.  No gradients."""
+    if cfg["L"] * cfg["F"] != 32:
+        raise NotImplementedError("hash field: the geometry net is instantiated for L*F = 32 hash features")
+    if res is None:
+        res = resolutions(cfg, origin.device)
+    if grid is not None:
+        span, seen = grid.ray_span(origin, dir, t_range)
+        empty = torch.stack([t_range[:, 0], torch.full_like(t_range[:, 0], -math.inf)], -1)  # (t1 is not finite: rejected, t_hit = t0)
+        t_range = torch.where(seen[:, None], span, empty).contiguous()
+    t, status, n_eval, sdf = hashtrace.trace(origin, dir, t_range, P["aabb"], P["hash.table"], res, cfg["log2_T"], P["hash.geo.0.weight"],
+                                             P["hash.geo.0.bias"], P["hash.geo.2.weight"][0], P["hash.geo.2.bias"][:1], eps=eps, step_scale=step_scale,
+                                             min_step=min_step, max_steps=max_steps, n_bisect=n_bisect)
+    hit = (status >= hashtrace.CONVERGED) & (status <= hashtrace.STARTS_INSIDE)
+    return Surface(t, status, n_eval, sdf, origin + t[:, None] * dir, hit)
+
+
+def render_surface(P, cfg, origin, dir, t_range, grid=None, prec=mlp.PREC_F32, differentiable=False, **trace_kw):
+    """Renders the field's SURFACE: trace_surface(P, cfg, origin, dir, t_range, grid, **trace_kw), then one sdf_gradient() and one forward() per
+    ray at the hit point with the unit direction.  Returns rgb (R,3), mask (R,1) = hit, depth (R,1) = t of the hit, normal (R,3) =
+    F.normalize(grad sdf).  A ray without a hit is parked outside the box (hi + (hi - lo), forward_compacted's rule) and renders zeros.
+    differentiable=False: the hit is a constant; rgb and normal are differentiable in the parameters at that fixed point, depth in nothing.
+    differentiable=True: depth = t - (sdf - sdf.detach()) / (grad.detach() . dir) -- the derivative of the implicit surface sdf(o + t d) = 0:
+    the VALUE is t bit for bit, the gradient reaches the table and the geometry net -- and the colour is evaluated at origin + depth * dir, so
+    that it gets a gradient through the point as well.  Rays with |grad . dir| < 1e-6 (grazing) keep the plain t."""
+    if "res" not in trace_kw or trace_kw["res"] is None:
+        trace_kw["res"] = resolutions(cfg, origin.device)
+    res = trace_kw["res"]
+    s = trace_surface(P, cfg, origin, dir, t_range, grid=grid, **trace_kw)
+    lo, hi = P["aabb"][0].detach(), P["aabb"][1].detach()
+    hit = s.hit[:, None]
+    park = (hi + (hi - lo)).expand_as(s.xyz)
+    unit = F.normalize(dir.detach(), dim=-1)
+    x = torch.where(hit, s.xyz, park).contiguous()
+    sdf, grad = sdf_gradient(P, cfg, x, res=res)
+    depth = s.t[:, None]
+    if differentiable:
+        gd = (grad.detach() * dir.detach()).sum(-1, keepdim=True)
+        ok = hit & (gd.abs() >= 1e-6)
+        depth = depth - torch.where(ok, (sdf - sdf.detach()) / torch.where(ok, gd, torch.ones_like(gd)), torch.zeros_like(gd))
+        x = torch.where(hit, origin.detach() + depth * dir.detach(), park)
+    rgb = forward(P, cfg, x, unit, spf=max(int(x.shape[0]), 1), prec=prec, res=res, get_density=False)[0]  # (zero outside the box: the parked rows)
+    mask = hit.to(rgb.dtype)
+    # (where, not a product with the mask: a rejected ray's t may be NaN)
+    return rgb * mask, mask, torch.where(hit, depth, torch.zeros_like(depth)), F.normalize(grad, dim=-1) * mask
