@@ -308,6 +308,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_hashtrace.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 19. Ray casting against a triangle mesh through a uniform face grid: first hit per ray (not in the reference, parity unpinned).
+ *     See lab4d_meshray.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_meshray.h"
+
 #ifdef __cplusplus
 }
 #endif

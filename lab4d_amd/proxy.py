@@ -98,6 +98,24 @@ def init_sdf_fn(verts, faces):
     return sdf_fn
 
 
+@torch.no_grad()
+def ray_range(grid, origin, dir, t_range, band=0.0):
+    """The per-ray sampling range the proxy mesh allows: `grid` is a lab4d_amd.meshray.MeshGrid of it, origin, dir (R, 3), t_range (R, 2) as
+    for grid.cast.  Two casts: the first hit, and the last hit as the first hit of the reversed ray (o + t1 d, -d) over [0, t1 - t0], mapped back
+    to t1 - t'.  Returns (t_range' (R, 2), hit (R,) bool): [t_first - band / |dir|, t_last + band / |dir|] cut to the given range (band: a
+    metric length, e.g. one cell of the field, that covers the proxy's distance from the surface it stands for); a ray that misses the
+    mesh gets the empty range of hashfield.trace_surface, [t0, -inf].  Feeds trace_surface, render_packed and sample_cam_rays(depth=...)."""
+    first = grid.cast(origin, dir, t_range)
+    t0, t1 = t_range[:, 0], t_range[:, 1]
+    back = grid.cast((origin + t1[:, None] * dir).contiguous(), (-dir).contiguous(), torch.stack([torch.zeros_like(t0), t1 - t0], -1).contiguous())
+    t_last = torch.where(back.hit, t1 - back.t, first.t)
+    t_last = torch.maximum(t_last, first.t)  # (one surface seen from both ends may come back a rounding in front of itself)
+    pad = float(band) / torch.linalg.vector_norm(dir, dim=-1)
+    lo, hi = torch.maximum(t0, first.t - pad), torch.minimum(t1, t_last + pad)
+    empty = torch.full_like(t1, -float("inf"))
+    return torch.stack([torch.where(first.hit, lo, t0), torch.where(first.hit, hi, empty)], -1).contiguous(), first.hit
+
+
 def grid_to_world(verts01, box):
     """marching_cubes' vertex transform from the unit cube to the box (geom_utils.py:492-493)."""
     return verts01 * (box[1:] - box[:1]) + box[:1]
