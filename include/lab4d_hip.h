@@ -314,6 +314,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_meshray.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 20. Closest point and signed distance from points to a triangle mesh through the face grid of 19, the sign from the pseudonormal of the
+ *     closest feature (not in the reference, parity unpinned).  See lab4d_meshnear.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_meshnear.h"
+
 #ifdef __cplusplus
 }
 #endif

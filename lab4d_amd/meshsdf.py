@@ -42,15 +42,28 @@ def _check(verts, faces, pts):
 
 
 @torch.no_grad()
-def signed_distance(verts, faces, pts, n_slices=None, return_face=False, return_closest=False, work=None):
+def signed_distance(verts, faces, pts, n_slices=None, return_face=False, return_closest=False, work=None, grid=None):
     """verts (V,3) fp32, faces (F,3) int32, pts (...,3) fp32, all on the device -> sdf of shape pts.shape[:-1], negative inside; then, if
     asked for, face (the same shape, int32: the winning face, -1 without one) and closest (..., 3).  A non-finite point gives NaN, a mesh
     without a valid face +inf.
     n_slices: how many ways the faces are split across blocks; default `default_slices(N, F)` =
     max(1, min(ceil(F / 256), 1024 // ceil(N / 256))).  The distance, the face and the closest point do not depend on it.
     work: a preallocated float32 buffer of at least `work_words(N, n_slices)` elements (for graph capture: no allocation besides the
-    outputs); default: allocated here.  Queries whose work buffer would pass 2^31 words run in chunks of points."""
+    outputs); default: allocated here.  Queries whose work buffer would pass 2^31 words run in chunks of points.
+    grid: a lab4d_amd.meshray.MeshGrid built from these very `verts` and `faces` tensors (checked by storage and shape): the query goes
+    through `grid.closest` (include/lab4d_meshnear.h) instead of every face -- the same distance, face and closest point word for word, the
+    sign from the pseudonormal of the closest feature with the orientation taken from the mesh's signed volume (on a closed mesh the winding
+    number's sign away from the surface; on an open one the side of the nearest feature).  n_slices and work are not used then.  Default
+    None: brute force, as before."""
     _check(verts, faces, pts)
+    if grid is not None:
+        if not hasattr(grid, "closest") or (grid.verts.data_ptr(), grid.verts.shape, grid.faces.data_ptr(), grid.faces.shape) != (
+                verts.data_ptr(), verts.shape, faces.data_ptr(), faces.shape):
+            raise RuntimeError("lab4d_amd.meshsdf: grid must be a lab4d_amd.meshray.MeshGrid of this mesh, built from these verts and faces tensors "
+                               "(%d vertices, %d faces): the same storage, not a copy" % (verts.shape[0], faces.shape[0]))
+        near = grid.closest(pts.detach())
+        out = (near.sdf,) + ((near.face,) if return_face else ()) + ((near.closest,) if return_closest else ())
+        return out[0] if len(out) == 1 else out
     verts, faces, pts = verts.detach(), faces.detach(), pts.detach()
     lead = pts.shape[:-1]
     flat = pts.reshape(-1, 3)

@@ -93,14 +93,16 @@ class OccupancyGrid:
         return depth.reshape(*lead, int(n_depth), 1).contiguous(), hit.reshape(lead)
 
     @torch.no_grad()
-    def seed_from_mesh(self, verts, faces, band=0.0):
+    def seed_from_mesh(self, verts, faces, band=0.0, grid=None):
         """Seed the grid from a mesh (verts (V,3) fp32, faces (F,3) int32 on the device) instead of waiting for the field's own density: the
         signed distance (lab4d_amd.meshsdf.signed_distance) at `cell_centers()` goes through `update()` as a density of 2 * thresh + 1
         where sdf <= band + half the cell diagonal, and 0 elsewhere.  The margin makes the seed conservative: the distance is 1-Lipschitz
         and no point of a cell is farther than half its diagonal from the centre, so every point of the box with sdf <= band lies in a
-        cell whose bit is set.  The usual EMA carries on from there: later updates with the field's density decay the seed."""
+        cell whose bit is set.  The usual EMA carries on from there: later updates with the field's density decay the seed.
+        grid: a lab4d_amd.meshray.MeshGrid of the mesh: the cell-centre query walks it (signed_distance(..., grid=grid)) instead of every
+        face; default None: brute force, as before."""
         from . import meshsdf
-        sdf = meshsdf.signed_distance(verts, faces, self.cell_centers())
+        sdf = meshsdf.signed_distance(verts, faces, self.cell_centers(), grid=grid)
         half_diag = 0.5 * torch.linalg.vector_norm((self.aabb[1] - self.aabb[0]) / self.G)
         density = torch.where(sdf <= float(band) + half_diag, 2.0 * self.thresh + 1.0, 0.0).to(torch.float32)
         return self.update(density)

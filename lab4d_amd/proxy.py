@@ -76,12 +76,14 @@ def extract_mesh(P, aabb, grid_size=64, level=0.0, code_base=None, code_vis=None
     return verts, faces, bounds
 
 
-def init_sdf_fn(verts, faces):
+def init_sdf_fn(verts, faces, grid=False):
     """NeRF.get_init_sdf_fn (nerf.py:217-230) on the device: from a mesh (vertices (V,3), faces (F,3); tensors, or the numpy arrays of a
     trimesh.Trimesh / lab4d_amd.mesh.Mesh) the callable `pts (N,3) -> sdf (N,1)`, negative inside, that geometry_init fits the field to
     (nerf.py:251-295).  The reference builds a pysdf.SDF on the host and copies every batch of points there and back; here the mesh is
-    moved to the points' device once and lab4d_amd.meshsdf.signed_distance answers in place."""
-    cache = {}
+    moved to the points' device once and lab4d_amd.meshsdf.signed_distance answers in place.  grid=True: one lab4d_amd.meshray.MeshGrid per
+    device is built next to the cached mesh and the query walks it (signed_distance(..., grid=...): the same distance, the sign from the
+    pseudonormal of the closest feature); the default answers by brute force, as before."""
+    cache, grids = {}, {}
 
     def mesh_on(device):
         if device not in cache:
@@ -92,7 +94,10 @@ def init_sdf_fn(verts, faces):
 
     def sdf_fn(pts):
         v, f = mesh_on(pts.device)
-        sdf = _meshsdf.signed_distance(v, f, pts.detach().to(torch.float32).contiguous())
+        if grid and pts.device not in grids:
+            from . import meshray as _meshray
+            grids[pts.device] = _meshray.MeshGrid(v, f)
+        sdf = _meshsdf.signed_distance(v, f, pts.detach().to(torch.float32).contiguous(), grid=grids[pts.device] if grid else None)
         return sdf[..., None].to(pts.dtype)
 
     return sdf_fn
