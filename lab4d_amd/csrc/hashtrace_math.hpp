@@ -1,16 +1,16 @@
 // Sphere tracing of the hash field's SDF to one surface hit per ray (csrc/hashtrace.hip; contract: include/lab4d_hashtrace.h).  Plain C++
-// (LAB4D_HD convention) on top of hashsdf_math.hpp (the table gather), occgrid_math.hpp (to_x01, the rounded arithmetic) and packed_math.hpp
-// (dir_length, point_at), none of them changed: the kernel and the CPU twin tests/host_harness/hashtrace/hashtrace_host.cpp call the same
-// functions.  The reference has no hash field and no tracer, so the rules are this repository's own; the method is Hart 1996, "Sphere
-// tracing", with a sign-change fallback for a field that is an SDF only approximately.
+// (LAB4D_HD convention) on top of hashsdf_math.hpp (the table gather), occgrid_math.hpp (to_x01, the rounded arithmetic) and ray_math.hpp
+// (dir_length, point_at, clip_ray: the one statement of RAY, REJECT and CLIP): the kernel and the CPU twin
+// tests/host_harness/hashtrace/hashtrace_host.cpp call the same functions.  The reference has no hash field and no tracer, so the rules are this
+// repository's own; the method is Hart 1996, "Sphere tracing", with a sign-change fallback for a field that is an SDF only approximately.
 //
-// RAY        o + t * d, t in [t0, t1], d of any length; len = |d| as packed_math.hpp rounds it (dir_length).  eps > 0: the hit threshold on
+// RAY        o + t * d, t in [t0, t1], d of any length; len = |d| as ray_math.hpp rounds it (dir_length).  eps > 0: the hit threshold on
 //            |sdf| in world units; 0 < step_scale <= 1; min_step > 0: a metric length in world units; 1 <= max_steps <= 1024;
 //            0 <= n_bisect <= 32.
 // REJECT     a non-finite o, d, t0 or t1, t0 > t1, len == 0, or a box without extent: status MISS, t_hit = t0, n_eval = 0, sdf_hit = 0.
-// CLIP       [t0, t1] is cut to the box with the slab test of occgrid_math.hpp (SPAN), restated here because ray_span does not return it: in
-//            x01 space, an axis whose d01 is zero or whose 1 / d01 is not finite is PARALLEL -- always satisfied when 0 <= o01 <= 1, never
-//            otherwise -- and no inf or NaN arithmetic occurs.  An empty clip is handled like a rejected ray.  Otherwise t_enter <= t_exit.
+// CLIP       ray_math.hpp's clip_ray cuts [t0, t1] to the box (the slab test in x01 space; a parallel axis is always or never satisfied, no inf or
+//            NaN arithmetic).  An empty clip is handled like a rejected ray: the tracer asks for code 2 alone, so the order of clip_ray's checks
+//            does not show here.  Otherwise t_enter <= t_exit.
 // EVAL       p = o + t * d (product and sum rounded on their own: point_at), x01 = (p - lo) / (hi - lo) (to_x01) CLAMPED to [0, 1] per axis
 //            (rounding may push an end point out of the box; the constant sdf outside the box is never traced), s = the fused evaluator's sdf
 //            at x01: gather_enc of hashsdf_math.hpp, then hidden_sdf below -- hidden() without v and without the mask.
@@ -26,12 +26,13 @@
 // that are in different phases still share the gather and the net, and the evaluator is inlined once.
 #pragma once
 #include "hashsdf_math.hpp"
-#include "packed_math.hpp"
+#include "occgrid_math.hpp"
+#include "ray_math.hpp"
 
 namespace lab4d_trace {
 namespace hs = lab4d_hsdf;
 namespace occ = lab4d_occ;
-namespace pk = lab4d_packed;
+namespace ray = lab4d_ray;
 using lab4d_rn::add_rn;
 using lab4d_rn::div_rn;
 using lab4d_rn::finite_f;
@@ -79,38 +80,15 @@ LAB4D_HD float sdf_at(const float* x01, const float* table, const int* res, int 
   return hidden_sdf(enc, W1, b1, w2, b2);
 }
 
-// REJECT and CLIP: false for a ray that is rejected or misses the box; otherwise *t_enter <= *t_exit and *len = |d| > 0
+// REJECT and CLIP as the tracer asks them of ray_math.hpp's clip_ray: true iff the ray enters the loop; then *t_enter <= *t_exit and *len = |d| > 0
 LAB4D_HD bool clip_ray(const float* o, const float* d, float t0, float t1, const float* aabb, float* t_enter, float* t_exit, float* len) {
-  if (!(finite_f(t0) && finite_f(t1) && t0 <= t1)) return false;
-  float tmin = t0, tmax = t1;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float ext = aabb[3 + a] - aabb[a];
-    if (!(finite_f(o[a]) && finite_f(d[a]) && finite_f(ext) && ext > 0.f)) return false;
-    const float o01 = div_rn(o[a] - aabb[a], ext), d01 = div_rn(d[a], ext);
-    if (!finite_f(o01)) return false;
-    const float inv = d01 != 0.f ? div_rn(1.f, d01) : 0.f;
-    if (!(d01 != 0.f && finite_f(inv))) {  // parallel
-      if (!(o01 >= 0.f && o01 <= 1.f)) return false;
-      continue;
-    }
-    const float ta = mul_rn(0.f - o01, inv), tb = mul_rn(1.f - o01, inv);
-    const float tn = ta < tb ? ta : tb, tf = ta < tb ? tb : ta;
-    if (tn > tmin) tmin = tn;
-    if (tf < tmax) tmax = tf;
-  }
-  if (!(tmin <= tmax)) return false;
-  *len = pk::dir_length(d);
-  if (!(*len > 0.f)) return false;
-  *t_enter = tmin;
-  *t_exit = tmax;
-  return true;
+  return ray::clip_ray(o, d, t0, t1, aabb, t_enter, t_exit, len) == 2;
 }
 
 // x01 of the ray's point at t, clamped into the box
 LAB4D_HD void x01_at(const float* o, const float* d, float t, const float* aabb, float* x01) {
   float p[3];
-  pk::point_at(o, d, t, p);
+  ray::point_at(o, d, t, p);
 #pragma unroll
   for (int a = 0; a < 3; ++a) x01[a] = fminf(fmaxf(occ::to_x01(p[a], aabb[a], aabb[3 + a]), 0.f), 1.f);
 }

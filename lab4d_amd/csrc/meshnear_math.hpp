@@ -1,14 +1,14 @@
 // Closest point and signed distance from points to a triangle mesh through the face grid of meshray_math.hpp (csrc/meshnear.hip; contract:
 // include/lab4d_meshnear.h, where every rule is written down once).  Plain C++ behind LAB4D_HD on hd_math.hpp's individually rounded products,
-// sums, quotients and roots, on meshsdf_math.hpp (dot_rn, point_finite: unchanged) and on meshray_math.hpp (Quad, grid_coord, the packed faces and
-// the lists: unchanged).  The kernel runs find_nearest one lane per point, the CPU twin tests/host_harness/meshnear/meshnear_host.cpp compiles the
-// same text with g++ (-ffp-contract=off) as a serial loop, and the GPU suite holds the kernel's d2, face, closest point and region bit for bit
+// sums, quotients and roots, on meshsdf_math.hpp (closest_reg and its Region, cross_rn, dot_rn, point_finite) and on meshray_math.hpp (Quad,
+// load_face, cell_of, plane_at, the packed faces and the lists).  The kernel runs find_nearest one lane per point, the CPU twin
+// tests/host_harness/meshnear/meshnear_host.cpp compiles the same text with g++ (-ffp-contract=off) as a serial loop, and the GPU suite holds the kernel's d2, face, closest point and region bit for bit
 // to that twin, and the sign wherever the region is a face or an edge (a vertex region's atan2f is each side's own, as the winding term of
 // meshsdf_math.hpp is).
 //
-// DISTANCE, TIES, VALID, EDGES  meshsdf_math.hpp's.  closest_reg below restates closest_d2 with the region as an extra result: the same
-//            operations in the same order (tests/test_meshnear_host.py holds the two bit-equal in d2 and q); the smallest d2 wins, ties go to the
-//            lowest face index whatever the order of the walk (d2 < best, or d2 == best and f < best's face; a d2 that is not < +inf never wins).
+// DISTANCE, TIES, VALID, EDGES  meshsdf_math.hpp's.  closest_reg is the brute-force query's own function (closest_d2 is it without the region);
+//            the smallest d2 wins, ties go to the lowest face index whatever the order of the walk (d2 < best, or d2 == best and f < best's
+//            face; a d2 that is not < +inf never wins).
 // REGION     0 face, 1 / 2 / 3 edge ab / ac / bc, 4 / 5 / 6 vertex a / b / c of the winning face; -1 without one.
 // SEARCH     shells of cells around the cell of p, see find_nearest and the header's error argument for the margin.
 // SIGN       the pseudonormal of the closest feature (Baerentzen & Aanaes 2005), from the listed faces of q's cell: see feature_side.
@@ -24,6 +24,11 @@ using lab4d_rn::inf_f;
 using lab4d_rn::mul_rn;
 using lab4d_rn::nan_f;
 using lab4d_rn::sqrt_rn;
+using mr::cell_of;
+using mr::load_face;
+using mr::plane_at;
+using msdf::closest_reg;
+using msdf::cross_rn;
 using msdf::dot_rn;
 
 constexpr int kBlock = 256;                        // points per workgroup
@@ -31,59 +36,10 @@ constexpr float kMarginCell = 0.015625f;           // 2^-6 of a cell's width
 constexpr float kMarginReach = 1.52587890625e-5f;  // 2^-16 of |p - lo| + |p - hi|
 constexpr float kMarginBox = 9.5367431640625e-7f;  // 2^-20 of |lo| + |hi|
 
-enum Region { kFace = 0, kEdgeAB = 1, kEdgeAC = 2, kEdgeBC = 3, kVertA = 4, kVertB = 5, kVertC = 6 };
-
-// msdf::closest_d2, restated: the same operations in the same order, and which branch was taken.
-LAB4D_HD float closest_reg(float px, float py, float pz, float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
-                           float& qx, float& qy, float& qz, int32_t& region) {
-  const float abx = bx - ax, aby = by - ay, abz = bz - az;
-  const float acx = cx - ax, acy = cy - ay, acz = cz - az;
-  const float apx = px - ax, apy = py - ay, apz = pz - az;
-  const float d1 = dot_rn(abx, aby, abz, apx, apy, apz), d2 = dot_rn(acx, acy, acz, apx, apy, apz);
-  const float bpx = px - bx, bpy = py - by, bpz = pz - bz;
-  const float d3 = dot_rn(abx, aby, abz, bpx, bpy, bpz), d4 = dot_rn(acx, acy, acz, bpx, bpy, bpz);
-  const float cpx = px - cx, cpy = py - cy, cpz = pz - cz;
-  const float d5 = dot_rn(abx, aby, abz, cpx, cpy, cpz), d6 = dot_rn(acx, acy, acz, cpx, cpy, cpz);
-  const float vc = mul_rn(d1, d4) - mul_rn(d3, d2);
-  const float vb = mul_rn(d5, d2) - mul_rn(d1, d6);
-  const float va = mul_rn(d3, d6) - mul_rn(d5, d4);
-  if (d1 <= 0.f && d2 <= 0.f) {
-    qx = ax, qy = ay, qz = az, region = kVertA;
-  } else if (d3 >= 0.f && d4 <= d3) {
-    qx = bx, qy = by, qz = bz, region = kVertB;
-  } else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {
-    const float t = div_rn(d1, d1 - d3);
-    qx = ax + mul_rn(t, abx), qy = ay + mul_rn(t, aby), qz = az + mul_rn(t, abz), region = kEdgeAB;
-  } else if (d6 >= 0.f && d5 <= d6) {
-    qx = cx, qy = cy, qz = cz, region = kVertC;
-  } else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {
-    const float t = div_rn(d2, d2 - d6);
-    qx = ax + mul_rn(t, acx), qy = ay + mul_rn(t, acy), qz = az + mul_rn(t, acz), region = kEdgeAC;
-  } else if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f) {
-    const float t = div_rn(d4 - d3, (d4 - d3) + (d5 - d6));
-    qx = bx + mul_rn(t, cx - bx), qy = by + mul_rn(t, cy - by), qz = bz + mul_rn(t, cz - bz), region = kEdgeBC;
-  } else {
-    const float sum = va + vb + vc;
-    const float v = div_rn(vb, sum), w = div_rn(vc, sum);
-    qx = ax + mul_rn(abx, v) + mul_rn(acx, w), qy = ay + mul_rn(aby, v) + mul_rn(acy, w), qz = az + mul_rn(abz, v) + mul_rn(acz, w), region = kFace;
-  }
-  const float ex = px - qx, ey = py - qy, ez = pz - qz;
-  return dot_rn(ex, ey, ez, ex, ey, ez);
-}
-
 struct Found {
   float sdf, d2, qx, qy, qz;
   int32_t face, region, n_tests, n_cells;  // n_cells: the cells the walk visited (a measurement, kept by the twin alone)
 };
-
-// the cell of x on one axis: 7j's grid coordinate, clamped into the grid (a NaN coordinate -- a box without extent -- gives cell 0)
-LAB4D_HD int cell_of(float x, float lo, float ext, int G) {
-  const float g = floorf(mr::grid_coord(x, lo, ext, G));
-  return g > 0.f ? (g < (float)(G - 1) ? (int)g : G - 1) : 0;
-}
-
-// the grid plane k (0 .. G) of an axis, from the integer index as 7j's walls are
-LAB4D_HD float plane_at(int k, float lo, float ext, int G) { return add_rn(lo, mul_rn(div_rn((float)k, (float)G), ext)); }
 
 // bound_r of one axis: the distance from p to the nearer OPEN side of [c0 - r, c0 + r] (a side with grid cells beyond it) minus the margin;
 // *open is set when the axis has an open side.  The result may be negative or NaN (an overflowing margin): the caller clamps, and stops on
@@ -105,9 +61,8 @@ LAB4D_HD float axis_bound(float p, float lo, float hi, int G, int c0, int r, flo
 
 // the three unit-length components of (b - a) x (c - a): rounded products, the correctly rounded root and quotients
 LAB4D_HD void unit_normal(const mr::Quad& a, const mr::Quad& b, const mr::Quad& c, float& nx, float& ny, float& nz) {
-  const float ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z;
-  const float wx = c.x - a.x, wy = c.y - a.y, wz = c.z - a.z;
-  const float cx = mul_rn(uy, wz) - mul_rn(uz, wy), cy = mul_rn(uz, wx) - mul_rn(ux, wz), cz = mul_rn(ux, wy) - mul_rn(uy, wx);
+  float cx, cy, cz;
+  cross_rn(b.x - a.x, b.y - a.y, b.z - a.z, c.x - a.x, c.y - a.y, c.z - a.z, cx, cy, cz);
   const float len = sqrt_rn(dot_rn(cx, cy, cz, cx, cy, cz));
   nx = div_rn(cx, len), ny = div_rn(cy, len), nz = div_rn(cz, len);
 }
@@ -118,7 +73,8 @@ LAB4D_HD bool same_point(const mr::Quad& v, float x, float y, float z) { return 
 LAB4D_HD float corner_angle(const mr::Quad& at, const mr::Quad& u, const mr::Quad& w) {
   const float e1x = u.x - at.x, e1y = u.y - at.y, e1z = u.z - at.z;
   const float e2x = w.x - at.x, e2y = w.y - at.y, e2z = w.z - at.z;
-  const float cx = mul_rn(e1y, e2z) - mul_rn(e1z, e2y), cy = mul_rn(e1z, e2x) - mul_rn(e1x, e2z), cz = mul_rn(e1x, e2y) - mul_rn(e1y, e2x);
+  float cx, cy, cz;
+  cross_rn(e1x, e1y, e1z, e2x, e2y, e2z, cx, cy, cz);
   return atan2f(sqrt_rn(dot_rn(cx, cy, cz, cx, cy, cz)), dot_rn(e1x, e1y, e1z, e2x, e2y, e2z));
 }
 
@@ -129,19 +85,20 @@ LAB4D_HD float corner_angle(const mr::Quad& at, const mr::Quad& u, const mr::Qua
 // cell's list.  A pass costs a face load per entry that can still be the next one.
 LAB4D_HD float feature_side(float px, float py, float pz, const Found& r, const float* aabb, int G, const mr::Quad* rec, const int32_t* cell_start,
                             const int32_t* cell_list) {
-  const mr::Quad wa = rec[3 * r.face], wb = rec[3 * r.face + 1], wc = rec[3 * r.face + 2];
+  mr::Quad wa, wb, wc;
+  load_face(rec, r.face, wa, wb, wc);
   const float ex = px - r.qx, ey = py - r.qy, ez = pz - r.qz;
-  if (r.region == kFace) {
-    const float ux = wb.x - wa.x, uy = wb.y - wa.y, uz = wb.z - wa.z;
-    const float wx = wc.x - wa.x, wy = wc.y - wa.y, wz = wc.z - wa.z;
-    return dot_rn(ex, ey, ez, mul_rn(uy, wz) - mul_rn(uz, wy), mul_rn(uz, wx) - mul_rn(ux, wz), mul_rn(ux, wy) - mul_rn(uy, wx));
+  if (r.region == msdf::kFace) {
+    float nx, ny, nz;
+    cross_rn(wb.x - wa.x, wb.y - wa.y, wb.z - wa.z, wc.x - wa.x, wc.y - wa.y, wc.z - wa.z, nx, ny, nz);
+    return dot_rn(ex, ey, ez, nx, ny, nz);
   }
   // the feature's one or two vertices, by selects
-  const bool edge = r.region <= kEdgeBC;
-  const bool first_a = r.region == kEdgeAB || r.region == kEdgeAC || r.region == kVertA;
-  const bool first_b = r.region == kEdgeBC || r.region == kVertB;
+  const bool edge = r.region <= msdf::kEdgeBC;
+  const bool first_a = r.region == msdf::kEdgeAB || r.region == msdf::kEdgeAC || r.region == msdf::kVertA;
+  const bool first_b = r.region == msdf::kEdgeBC || r.region == msdf::kVertB;
   const mr::Quad v0 = first_a ? wa : (first_b ? wb : wc);
-  const mr::Quad v1 = r.region == kEdgeAB ? wb : wc;  // (an edge's other end; unused for a vertex)
+  const mr::Quad v1 = r.region == msdf::kEdgeAB ? wb : wc;  // (an edge's other end; unused for a vertex)
   const int cx = cell_of(r.qx, aabb[0], aabb[3] - aabb[0], G), cy = cell_of(r.qy, aabb[1], aabb[4] - aabb[1], G),
             cz = cell_of(r.qz, aabb[2], aabb[5] - aabb[2], G);
   const int cell = cx + G * (cy + G * cz);  // (G <= 128: below 2^21; 3 f + 2 < 2^29 for n_faces <= 2^31 / 12)
@@ -153,14 +110,16 @@ LAB4D_HD float feature_side(float px, float py, float pz, const Found& r, const 
     for (int32_t j = lo; j < hi; ++j) {
       const int32_t f = cell_list[j];
       if (!(f > last && f < next)) continue;
-      const mr::Quad a = rec[3 * f], b = rec[3 * f + 1], c = rec[3 * f + 2];
+      mr::Quad a, b, c;
+      load_face(rec, f, a, b, c);
       const bool has0 = same_point(a, v0.x, v0.y, v0.z) || same_point(b, v0.x, v0.y, v0.z) || same_point(c, v0.x, v0.y, v0.z);
       const bool has1 = !edge || same_point(a, v1.x, v1.y, v1.z) || same_point(b, v1.x, v1.y, v1.z) || same_point(c, v1.x, v1.y, v1.z);
       if (a.w != 0.f && has0 && has1) next = f;
     }
     if (next == 2147483647) break;
     last = next;
-    const mr::Quad a = rec[3 * next], b = rec[3 * next + 1], c = rec[3 * next + 2];
+    mr::Quad a, b, c;
+    load_face(rec, next, a, b, c);
     float ux, uy, uz;
     unit_normal(a, b, c, ux, uy, uz);
     if (edge) {
@@ -202,7 +161,8 @@ LAB4D_HD Found find_nearest(float px, float py, float pz, const float* aabb, int
       ++r.n_cells;
       for (int32_t j = lo; j < hi; ++j) {
         const int32_t f = cell_list[j];
-        const mr::Quad a = rec[3 * f], b = rec[3 * f + 1], c = rec[3 * f + 2];
+        mr::Quad a, b, c;
+        load_face(rec, f, a, b, c);
         float qx, qy, qz;
         int32_t region;
         const float d2 = closest_reg(px, py, pz, a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, qx, qy, qz, region);

@@ -1,18 +1,18 @@
 // Ray casting against a triangle mesh through a uniform face grid (csrc/meshray.hip; contract: include/lab4d_meshray.h).  Plain C++ behind
 // LAB4D_HD on hd_math.hpp's individually rounded products, sums and quotients (no contraction anywhere that decides a result) and on
-// meshsdf_math.hpp's VALID rule (tri_valid / load_tri, unchanged): the kernels run these functions one lane per face or per ray, the CPU twin
+// meshsdf_math.hpp's VALID rule (tri_valid / load_tri) and on ray_math.hpp's RAY, REJECT and CLIP (dir_length, point_at, clip_ray: shared with
+// the sphere tracer).  The grid's own helpers (grid_coord, cell_of, plane_at, load_face) are stated here once for the ray caster and for the
+// nearest-point query of meshnear_math.hpp.  The kernels run these functions one lane per face or per ray, the CPU twin
 // tests/host_harness/meshray/meshray_host.cpp compiles them with g++ (-ffp-contract=off) as serial loops, and the GPU suite holds the kernel's
 // t, face, u, v and front bit for bit to that twin.  The reference has no ray caster: the rules are this repository's own.
 //
 // VALID      meshsdf_math.hpp: indices in [0, n_verts), nine finite coordinates, |(b - a) x (c - a)|^2 finite and > 0.  An invalid face is
 //            never hit and never binned.  A face is PACKED once as three 16-byte words {a xyz, valid}, {b xyz, 0}, {c xyz, 0}.
-// RAY        o + t * d, t in [t0, t1] in units of d, d of any length; len = |d| = the correctly rounded root of the three rounded squares added
-//            x, then y, then z (dir_length of packed_math.hpp, restated).  REJECT: a non-finite o, d, t0 or t1, t0 > t1, len == 0, or a box
-//            without extent: face = -1, t = t0, u = v = 0, front = 0, n_tests = 0.
-// CLIP       [t0, t1] is cut to the box with the slab test of hashtrace_math.hpp (clip_ray, restated): in x01 space an axis whose d01 is zero
-//            or whose 1 / d01 is not finite is PARALLEL -- always satisfied when 0 <= o01 <= 1, never otherwise --, no inf or NaN arithmetic
-//            occurs.  An empty clip is a MISS without a test.  Otherwise t_enter <= t_exit, and THE MESH IS CUT TO THE BOX: a face test
-//            accepts t in [t_enter, t_exit] (the whole clipped range, not the span of the cell it is made in).
+// RAY        ray_math.hpp's: o + t * d, t in [t0, t1] in units of d, d of any length; len = |d| (dir_length).  REJECT (clip_ray's code 0): a
+//            non-finite o, d, t0 or t1, t0 > t1, len == 0, or a box without extent: face = -1, t = t0, u = v = 0, front = 0, n_tests = 0.
+// CLIP       ray_math.hpp's clip_ray cuts [t0, t1] to the box, every reject before the first slab.  An empty clip (code 1) is a MISS without a
+//            test.  Otherwise (code 2) t_enter <= t_exit, and THE MESH IS CUT TO THE BOX: a face test accepts t in [t_enter, t_exit] (the whole
+//            clipped range, not the span of the cell it is made in).
 // INTERSECT  Woop, Benthin, Wald 2013, "Watertight ray/triangle intersection".  kz = argmax |d_k| (ties to the lowest axis), kx = (kz + 1) % 3,
 //            ky = (kx + 1) % 3, swapped if d[kz] < 0.  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].  Per vertex P' = P - o,
 //            Px = P'[kx] - Sx P'[kz], Py = P'[ky] - Sy P'[kz], Pz = Sz P'[kz].  U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax, every
@@ -32,16 +32,17 @@
 //            the step leaves the grid.  n_tests counts the face tests (for measurement: it depends on G and on nothing else).
 #pragma once
 #include "meshsdf_math.hpp"
+#include "ray_math.hpp"
 
 namespace lab4d_mray {
 namespace msdf = lab4d_msdf;
+using lab4d_ray::point_at;
 using lab4d_rn::add_rn;
 using lab4d_rn::dadd;
 using lab4d_rn::div_rn;
 using lab4d_rn::dmul;
 using lab4d_rn::finite_f;
 using lab4d_rn::mul_rn;
-using lab4d_rn::sqrt_rn;
 
 constexpr int kMaxG = 128;
 constexpr int kBlock = 256;               // lanes (rays, faces) per workgroup
@@ -60,8 +61,6 @@ struct Hit {
 
 LAB4D_HD float sel3(float x, float y, float z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
 
-LAB4D_HD float dir_length(const float* d) { return sqrt_rn(add_rn(add_rn(mul_rn(d[0], d[0]), mul_rn(d[1], d[1])), mul_rn(d[2], d[2]))); }
-
 // ---- packing and binning -----------------------------------------------------------------------------------------------------------------
 // face f of the mesh -> its three words; returns VALID
 LAB4D_HD bool pack_face(const float* verts, const int32_t* faces, int n_verts, long f, Quad* rec) {
@@ -73,8 +72,23 @@ LAB4D_HD bool pack_face(const float* verts, const int32_t* faces, int n_verts, l
   return ok;
 }
 
+// the three words of packed face f; I is the width of the index arithmetic (the ray caster's is 64-bit)
+template <class I>
+LAB4D_HD void load_face(const Quad* rec, I f, Quad& a, Quad& b, Quad& c) {
+  a = rec[3 * f], b = rec[3 * f + 1], c = rec[3 * f + 2];
+}
+
 // grid coordinate of x on one axis
 LAB4D_HD float grid_coord(float x, float lo, float ext, int G) { return mul_rn(div_rn(x - lo, ext), (float)G); }
+
+// the cell of x on one axis: the grid coordinate's floor, clamped into the grid (a NaN coordinate -- a box without extent -- gives cell 0)
+LAB4D_HD int cell_of(float x, float lo, float ext, int G) {
+  const float g = floorf(grid_coord(x, lo, ext, G));
+  return g > 0.f ? (g < (float)(G - 1) ? (int)g : G - 1) : 0;
+}
+
+// the grid plane k (0 .. G) of an axis, from the integer index
+LAB4D_HD float plane_at(int k, float lo, float ext, int G) { return add_rn(lo, mul_rn(div_rn((float)k, (float)G), ext)); }
 
 // The cells of a packed face: false when it is listed nowhere (invalid, a box without extent, wholly outside); else i0[a] <= i1[a] in [0, G)
 LAB4D_HD bool face_cells(const Quad* rec, const float* aabb, int G, int* i0, int* i1) {
@@ -94,35 +108,10 @@ LAB4D_HD bool face_cells(const Quad* rec, const float* aabb, int G, int* i0, int
 }
 
 // ---- the ray -------------------------------------------------------------------------------------------------------------------------------
-// REJECT and CLIP (hashtrace_math.hpp's clip_ray, restated): 0 = rejected, 1 = the clip is empty (a MISS), 2 = t_enter <= t_exit
+// REJECT and CLIP: ray_math.hpp's clip_ray (0 = rejected, 1 = the clip is empty: a MISS, 2 = t_enter <= t_exit) without |d|, which the cast does not use
 LAB4D_HD int clip_ray(const float* o, const float* d, float t0, float t1, const float* aabb, float* t_enter, float* t_exit) {
-  if (!(finite_f(t0) && finite_f(t1) && t0 <= t1)) return 0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float ext = aabb[3 + a] - aabb[a];
-    if (!(finite_f(o[a]) && finite_f(d[a]) && finite_f(ext) && ext > 0.f)) return 0;
-  }
-  if (!(dir_length(d) > 0.f)) return 0;
-  float tmin = t0, tmax = t1;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float ext = aabb[3 + a] - aabb[a];
-    const float o01 = div_rn(o[a] - aabb[a], ext), d01 = div_rn(d[a], ext);
-    if (!finite_f(o01)) return 0;
-    const float inv = d01 != 0.f ? div_rn(1.f, d01) : 0.f;
-    if (!(d01 != 0.f && finite_f(inv))) {  // parallel
-      if (!(o01 >= 0.f && o01 <= 1.f)) return 1;
-      continue;
-    }
-    const float ta = mul_rn(0.f - o01, inv), tb = mul_rn(1.f - o01, inv);
-    const float tn = ta < tb ? ta : tb, tf = ta < tb ? tb : ta;
-    if (tn > tmin) tmin = tn;
-    if (tf < tmax) tmax = tf;
-  }
-  if (!(tmin <= tmax)) return 1;
-  *t_enter = tmin;
-  *t_exit = tmax;
-  return 2;
+  float len;
+  return lab4d_ray::clip_ray(o, d, t0, t1, aabb, t_enter, t_exit, &len);
 }
 
 // the shear of INTERSECT, once per ray
@@ -177,18 +166,16 @@ LAB4D_HD bool intersect(const float* o, const Shear& s, float t_lo, float t_hi, 
 }
 
 // the parameter at which the ray crosses the grid plane k (0 .. G) of an axis
-LAB4D_HD float wall_t(int k, float lo, float ext, int G, float o, float d) {
-  const float x = add_rn(lo, mul_rn(div_rn((float)k, (float)G), ext));
-  return div_rn(x - o, d);
-}
+LAB4D_HD float wall_t(int k, float lo, float ext, int G, float o, float d) { return div_rn(plane_at(k, lo, ext, G) - o, d); }
 
 // One ray against the grid.  tris: n_faces packed faces; cell_start (G^3 + 1), cell_list: the lists.  Every member of the result is set.
 LAB4D_HD Hit cast_ray(const float* o, const float* d, float t0, float t1, const float* aabb, int G, const float* tris, int n_faces, const int32_t* cell_start,
                       const int32_t* cell_list) {
   Hit h;
   h.t = t0, h.u = 0.f, h.v = 0.f, h.face = -1, h.front = 0, h.n_tests = 0;
-  float t_enter, t_exit;
+  float t_enter, t_exit, p[3];
   if (n_faces == 0 || clip_ray(o, d, t0, t1, aabb, &t_enter, &t_exit) != 2) return h;
+  point_at(o, d, t_enter, p);
   const Shear s = make_shear(d);
   const Quad* rec = (const Quad*)tris;
   int c[3], step[3];
@@ -196,8 +183,7 @@ LAB4D_HD Hit cast_ray(const float* o, const float* d, float t0, float t1, const 
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const float ext = aabb[3 + a] - aabb[a];
-    const float g = floorf(grid_coord(add_rn(o[a], mul_rn(t_enter, d[a])), aabb[a], ext, G));
-    c[a] = g > 0.f ? (g < (float)(G - 1) ? (int)g : G - 1) : 0;
+    c[a] = cell_of(p[a], aabb[a], ext, G);
     step[a] = d[a] > 0.f ? 1 : (d[a] < 0.f ? -1 : 0);
     next[a] = lab4d_rn::inf_f();
     if (step[a] != 0) {
@@ -211,7 +197,8 @@ LAB4D_HD Hit cast_ray(const float* o, const float* d, float t0, float t1, const 
     const int32_t lo = cell_start[cell], hi = cell_start[cell + 1];
     for (int32_t j = lo; j < hi; ++j) {
       const int32_t f = cell_list[j];
-      const Quad qa = rec[3 * (long)f], qb = rec[3 * (long)f + 1], qc = rec[3 * (long)f + 2];
+      Quad qa, qb, qc;
+      load_face(rec, (long)f, qa, qb, qc);
       float t, u, v;
       int32_t front;
       ++h.n_tests;

@@ -8,8 +8,8 @@
 // VALID     a triangle (i0, i1, i2) is valid iff all three indices lie in [0, n_verts), all nine coordinates are finite, and the squared
 //           length of (b - a) x (c - a) is finite and > 0.  An invalid triangle is skipped, for the distance and for the sign.
 // DISTANCE  the closest point q of the triangle by region classification (vertex a, vertex b, edge ab, vertex c, edge ac, edge bc, face:
-//           Ericson, Real-Time Collision Detection, 5.1.5, in that order), d2 = |p - q|^2, d = sqrt(d2) correctly rounded.  Every product
-//           that feeds a sum or a comparison is rounded on its own (mul_rn, see hd_math.hpp, as for sqrt_rn); the quotients are the
+//           Ericson, Real-Time Collision Detection, 5.1.5, in that order: closest_reg, which the grid query of meshnear_math.hpp runs too),
+//           d2 = |p - q|^2, d = sqrt(d2) correctly rounded.  Every product that feeds a sum or a comparison is rounded on its own (mul_rn, see hd_math.hpp, as for sqrt_rn); the quotients are the
 //           correctly rounded division on both sides.  Over the faces the smallest d2 wins; a d2 that is not < +inf (overflow) never
 //           wins.  TIES go to the lowest face index: a strict < while walking the faces in ascending order, and a strict < in ascending
 //           slice order when partial results are combined.  d2, q and the winning face are therefore a pure function of the inputs,
@@ -41,13 +41,18 @@ LAB4D_HD long slice_lo(int s, int n_faces, int n_slices) { return (long)s * n_fa
 
 LAB4D_HD float dot_rn(float ax, float ay, float az, float bx, float by, float bz) { return mul_rn(ax, bx) + mul_rn(ay, by) + mul_rn(az, bz); }
 
+// n = u x w, every product rounded on its own.  With u = b - a, w = c - a: the face normal of VALID, of the mesh ray caster's front side and of
+// the nearest-point query's pseudonormals.
+LAB4D_HD void cross_rn(float ux, float uy, float uz, float wx, float wy, float wz, float& nx, float& ny, float& nz) {
+  nx = mul_rn(uy, wz) - mul_rn(uz, wy), ny = mul_rn(uz, wx) - mul_rn(ux, wz), nz = mul_rn(ux, wy) - mul_rn(uy, wx);
+}
+
 // v = the nine coordinates a, b, c of a triangle whose indices were in range
 LAB4D_HD bool tri_valid(const float* v) {
   for (int k = 0; k < 9; ++k)
     if (!finite_f(v[k])) return false;
-  const float ux = v[3] - v[0], uy = v[4] - v[1], uz = v[5] - v[2];
-  const float wx = v[6] - v[0], wy = v[7] - v[1], wz = v[8] - v[2];
-  const float nx = mul_rn(uy, wz) - mul_rn(uz, wy), ny = mul_rn(uz, wx) - mul_rn(ux, wz), nz = mul_rn(ux, wy) - mul_rn(uy, wx);
+  float nx, ny, nz;
+  cross_rn(v[3] - v[0], v[4] - v[1], v[5] - v[2], v[6] - v[0], v[7] - v[1], v[8] - v[2], nx, ny, nz);
   const float n2 = dot_rn(nx, ny, nz, nx, ny, nz);
   return finite_f(n2) && n2 > 0.f;
 }
@@ -67,9 +72,13 @@ LAB4D_HD bool load_tri(const float* verts, const int32_t* faces, int n_verts, lo
   return tri_valid(v);
 }
 
-// closest point of triangle (a, b, c) to p -> (qx, qy, qz); returns d2.  Scalars, not arrays: everything stays in registers on the device.
-LAB4D_HD float closest_d2(float px, float py, float pz, float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
-                          float& qx, float& qy, float& qz) {
+// which feature of the triangle holds the closest point (the nearest-point query of meshnear_math.hpp reports it and signs by it)
+enum Region { kFace = 0, kEdgeAB = 1, kEdgeAC = 2, kEdgeBC = 3, kVertA = 4, kVertB = 5, kVertC = 6 };
+
+// closest point of triangle (a, b, c) to p -> (qx, qy, qz) and the region it lies in; returns d2.  Scalars, not arrays: everything stays in
+// registers on the device.  The ONE statement of DISTANCE: the brute-force query and the grid query both run it.
+LAB4D_HD float closest_reg(float px, float py, float pz, float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
+                           float& qx, float& qy, float& qz, int32_t& region) {
   const float abx = bx - ax, aby = by - ay, abz = bz - az;
   const float acx = cx - ax, acy = cy - ay, acz = cz - az;
   const float apx = px - ax, apy = py - ay, apz = pz - az;
@@ -81,28 +90,35 @@ LAB4D_HD float closest_d2(float px, float py, float pz, float ax, float ay, floa
   const float vc = mul_rn(d1, d4) - mul_rn(d3, d2);
   const float vb = mul_rn(d5, d2) - mul_rn(d1, d6);
   const float va = mul_rn(d3, d6) - mul_rn(d5, d4);
-  if (d1 <= 0.f && d2 <= 0.f) {  // vertex a
-    qx = ax, qy = ay, qz = az;
-  } else if (d3 >= 0.f && d4 <= d3) {  // vertex b
-    qx = bx, qy = by, qz = bz;
-  } else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {  // edge ab
+  if (d1 <= 0.f && d2 <= 0.f) {
+    qx = ax, qy = ay, qz = az, region = kVertA;
+  } else if (d3 >= 0.f && d4 <= d3) {
+    qx = bx, qy = by, qz = bz, region = kVertB;
+  } else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {
     const float t = div_rn(d1, d1 - d3);
-    qx = ax + mul_rn(t, abx), qy = ay + mul_rn(t, aby), qz = az + mul_rn(t, abz);
-  } else if (d6 >= 0.f && d5 <= d6) {  // vertex c
-    qx = cx, qy = cy, qz = cz;
-  } else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {  // edge ac
+    qx = ax + mul_rn(t, abx), qy = ay + mul_rn(t, aby), qz = az + mul_rn(t, abz), region = kEdgeAB;
+  } else if (d6 >= 0.f && d5 <= d6) {
+    qx = cx, qy = cy, qz = cz, region = kVertC;
+  } else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {
     const float t = div_rn(d2, d2 - d6);
-    qx = ax + mul_rn(t, acx), qy = ay + mul_rn(t, acy), qz = az + mul_rn(t, acz);
-  } else if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f) {  // edge bc
+    qx = ax + mul_rn(t, acx), qy = ay + mul_rn(t, acy), qz = az + mul_rn(t, acz), region = kEdgeAC;
+  } else if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f) {
     const float t = div_rn(d4 - d3, (d4 - d3) + (d5 - d6));
-    qx = bx + mul_rn(t, cx - bx), qy = by + mul_rn(t, cy - by), qz = bz + mul_rn(t, cz - bz);
-  } else {  // face
+    qx = bx + mul_rn(t, cx - bx), qy = by + mul_rn(t, cy - by), qz = bz + mul_rn(t, cz - bz), region = kEdgeBC;
+  } else {
     const float sum = va + vb + vc;
     const float v = div_rn(vb, sum), w = div_rn(vc, sum);
-    qx = ax + mul_rn(abx, v) + mul_rn(acx, w), qy = ay + mul_rn(aby, v) + mul_rn(acy, w), qz = az + mul_rn(abz, v) + mul_rn(acz, w);
+    qx = ax + mul_rn(abx, v) + mul_rn(acx, w), qy = ay + mul_rn(aby, v) + mul_rn(acy, w), qz = az + mul_rn(abz, v) + mul_rn(acz, w), region = kFace;
   }
   const float ex = px - qx, ey = py - qy, ez = pz - qz;
   return dot_rn(ex, ey, ez, ex, ey, ez);
+}
+
+// closest_reg without the region
+LAB4D_HD float closest_d2(float px, float py, float pz, float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
+                          float& qx, float& qy, float& qz) {
+  int32_t region;
+  return closest_reg(px, py, pz, ax, ay, az, bx, by, bz, cx, cy, cz, qx, qy, qz, region);
 }
 
 // half the signed solid angle of the triangle seen from p: atan2(det, ...) of SIGN

@@ -3,7 +3,8 @@
 // (start, count), and that list is composited directly -- Mueller et al. 2022, section 5.4 / appendix E.  The reference has no counterpart
 // (nnutils/nerf.py:98 is a TODO), so the rules below are this repository's own; the compositing itself is the reference's compute_weights
 // + integrate (utils/render_utils.py:99-160) on every ray alone, at D = the ray's own count.
-// Plain C++ behind LAB4D_HD over the helpers of occgrid_math.hpp (to_x01, sample_mask, ray_span, mul_rn / add_rn / div_rn, unchanged): the
+// Plain C++ behind LAB4D_HD over the helpers of occgrid_math.hpp (to_x01, sample_mask, ray_span, mul_rn / add_rn / div_rn) and over
+// ray_math.hpp, where |d| (dir_length) and the point at t (point_at) live for every ray kernel; both keep their names here.  The
 // kernels run these functions one lane per ray, tests/host_harness/packed_host.cpp compiles them with g++ (-ffp-contract=off) as serial
 // loops, and the GPU suite holds the march kernels word for word to that twin.
 //
@@ -27,21 +28,14 @@
 //            without samples: mask = 0 and every output 0 (mode 2 included), no NaN.
 #pragma once
 #include "occgrid_math.hpp"
+#include "ray_math.hpp"
 
 namespace lab4d_packed {
 namespace occ = lab4d_occ;
-using lab4d_rn::sqrt_rn;  // the correctly rounded fp32 square root on both sides (hd_math.hpp)
+using lab4d_ray::dir_length;  // |d| and o + t * d: ray_math.hpp's, shared with the tracer and the mesh ray caster
+using lab4d_ray::point_at;
 
 LAB4D_HD float cand_t(float t0, int k, float dt) { return occ::add_rn(t0, occ::mul_rn((float)k + 0.5f, dt)); }
-
-LAB4D_HD float dir_length(const float* d) {
-  return sqrt_rn(occ::add_rn(occ::add_rn(occ::mul_rn(d[0], d[0]), occ::mul_rn(d[1], d[1])), occ::mul_rn(d[2], d[2])));
-}
-
-LAB4D_HD void point_at(const float* o, const float* d, float t, float* p) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) p[a] = occ::add_rn(o[a], occ::mul_rn(t, d[a]));
-}
 
 // the point of a parked row: outside the box on every axis
 LAB4D_HD void park_point(const float* aabb, float* p) {

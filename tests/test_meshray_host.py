@@ -228,6 +228,22 @@ def test_degenerate_rays(host):
     assert grid["cell_list"].size == 0 and (got["face"] == -1).all() and (got["n_tests"] == 0).all()
 
 
+def test_clip_rejects_before_it_tests_a_slab(host):
+    """csrc/ray_math.hpp's clip_ray, shared with the sphere tracer: every REJECT is decided before the first slab, so a rejected ray that also
+    misses the box has code 0, not 1.  On the unit box, each ray with the x axis parallel (d.x == 0) and o.x outside it: a NaN in d.y, a zero
+    direction, t0 > t1 -- code 0 --, and a finite non-zero ray -- code 1; t_clip stays (t0, t0).  The tracer's entry lets none of them in."""
+    import hashtrace_checks as TC
+    o = np.array([[2, 0.5, 0.5]] * 4, np.float32)
+    d = np.array([[0, np.nan, 1], [0, 0, 0], [0, 0, 1], [0, 0, 1]], np.float32)
+    tr = np.array([[0.25, 4], [0.25, 4], [3, 2], [0.25, 4]], np.float32)
+    box = np.array([0, 0, 0, 1, 1, 1], np.float32)
+    t_clip, code = np.full((4, 2), 7.0, np.float32), np.full(4, 7, np.int32)
+    host.meshray_host_clip(o.ctypes.data, d.ctypes.data, tr.ctypes.data, box.ctypes.data, 4, t_clip.ctypes.data, code.ctypes.data)
+    assert code.tolist() == [0, 0, 0, 1] and np.array_equal(t_clip, tr[:, [0, 0]]), (code, t_clip)
+    t_clip, ok = TC.host_clip(TC.build_host(), o, d, tr, {"aabb": torch.from_numpy(box.reshape(2, 3))})
+    assert not ok.any() and np.array_equal(t_clip, tr[:, [0, 0]]), (ok, t_clip)
+
+
 def test_twin_runs_clean_under_the_sanitizers():
     """the stand-alone program beside the twin, AddressSanitizer + UndefinedBehaviorSanitizer, run directly with nothing preloaded"""
     os.makedirs(os.path.join(host_twin.BUILD, os.path.dirname(MC.TWIN)), exist_ok=True)
