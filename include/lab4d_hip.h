@@ -320,6 +320,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_meshnear.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 21. Merge of two packed sample lists per ray by depth and the gather of per-row values through it: 3b for the packed layout --
+ *     nnutils/multifields.py:339-398 (MultiFields.compose_fields).  See lab4d_pmerge.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_pmerge.h"
+
 #ifdef __cplusplus
 }
 #endif

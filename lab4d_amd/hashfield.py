@@ -17,8 +17,9 @@ grid.ray_depths() places a ray's samples between its first and last occupied cel
 fixed step through the occupied cells only (packed.march), the field runs on the packed list of kept samples, and the list is composited per ray
 (packed.composite); nothing of size rays x samples-per-ray exists.  render_packed_pruned() also drops the rows BEHIND the surface before the
 differentiable field runs: density() of the kept rows without gradients, packed.prune by transmittance and opacity, forward() on the survivors
-(include/lab4d_prune.h).  with_distortion=True on either adds the distortion loss of the list per ray (include/lab4d_distort.h).  All of it
-is opt-in.
+(include/lab4d_prune.h).  with_distortion=True on either adds the distortion loss of the list per ray (include/lab4d_distort.h).
+render_packed_pair() composites TWO hash fields, an object in front of a scene, into one image: each is marched through its own grid and the two
+packed lists are z-merged per ray (include/lab4d_pmerge.h).  All of it is opt-in.
 
 The SDF as an SDF: sdf_gradient() returns the sdf with its gradient in the point from one fused kernel (hashsdf.py, include/lab4d_hashsdf.h),
 differentiable in the table and the geometry net; eikonal_loss() and normals() build on it (the counterparts of nnutils/nerf.py:416-493), and
@@ -240,6 +241,35 @@ def render_packed_pruned(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.P
     if with_normal:
         out += (rendered["normal"],)
     return out + (_packed_distortion(dens_s, kept, dt),) if with_distortion else out
+
+
+PackedField = collections.namedtuple("PackedField", "P cfg grid origin dir t_range dt cap")
+PairRender = collections.namedtuple("PairRender", "rgb mask depth mask_a mask_b total_a overflow_a total_b overflow_b total overflow")
+
+
+def render_packed_pair(a, b, merged_cap=None, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res_a=None, res_b=None):
+    """Two hash fields composited into one image: an object in front of a scene, the "comp" configurations' compose_fields
+    (nnutils/multifields.py:339-398) on packed lists (include/lab4d_pmerge.h).  a, b: a PackedField each -- its parameters and cfg, its
+    occupancy grid, the SAME R rays as origin, dir (R,3) and t_range (R,2) in the field's OWN frame, its step dt and its STATIC capacity.
+    Both must measure t in the same units along a ray (a rigid transform between the frames keeps it; a scale does not).  Each field is
+    marched through its own grid (packed.march) and evaluated on its own rows (forward()); packed.merge z-sorts the two lists per ray
+    (a tie goes to `a`) into at most merged_cap rows (default a.cap + b.cap: no overflow), packed.merge_rows gathers rgb, the density,
+    density_a (b's block zero) and density_b (a's block zero), and packed.composite renders them over the merged (start, count) with
+    depth = merged.t.  mask_a / mask_b are the rendered density_a / density_b over (their sum + 1e-6), as utils/render_utils.py:172-183
+    turns density_fg / density_bg into mask_fg / mask_bg.  -> PairRender(rgb (R,3), mask, depth, mask_a, mask_b (R,1), total_a,
+    overflow_a, total_b, overflow_b (the marches'), total, overflow (the merge's)).  Gradients reach both fields' tables, Linears and
+    logibeta."""
+    rays_a = packed.march(a.grid, a.origin, a.dir, a.t_range, a.dt, a.cap, k_max=k_max)
+    rays_b = packed.march(b.grid, b.origin, b.dir, b.t_range, b.dt, b.cap, k_max=k_max)
+    rgb_a, dens_a = forward(a.P, a.cfg, rays_a.xyz, rays_a.dirs, spf=max(int(a.cap), 1), prec=prec, res=res_a, table_grad_f16=table_grad_f16)
+    rgb_b, dens_b = forward(b.P, b.cfg, rays_b.xyz, rays_b.dirs, spf=max(int(b.cap), 1), prec=prec, res=res_b, table_grad_f16=table_grad_f16)
+    merged = packed.merge(rays_a, rays_b, cap=merged_cap)
+    fields = {"rgb": packed.merge_rows(merged, rgb_a, rgb_b), "depth": merged.t[:, None], "density_a": packed.merge_rows(merged, a=dens_a),
+              "density_b": packed.merge_rows(merged, b=dens_b)}
+    rendered, mask = packed.composite(packed.merge_rows(merged, dens_a, dens_b), merged.deltas, fields, merged)
+    density_sum = rendered["density_a"] + rendered["density_b"] + 1e-6
+    return PairRender(rendered["rgb"], mask, rendered["depth"], rendered["density_a"] / density_sum, rendered["density_b"] / density_sum, rays_a.total,
+                      rays_a.overflow, rays_b.total, rays_b.overflow, merged.total, merged.overflow)
 
 
 Surface = collections.namedtuple("Surface", "t status n_eval sdf xyz hit")

@@ -4,7 +4,9 @@ step through the occupied cells of an occgrid.OccupancyGrid and emits the kept s
 (nnutils/nerf.py:98 is a TODO); the rules are written down in the header and in csrc/packed_math.hpp.  `prune` (include/lab4d_prune.h,
 csrc/prune.hip) drops the rows of such a list that lie behind the point where their ray has become opaque, and the rows without opacity,
 given the density of the rows: the step between a density pass without gradients and the differentiable field.  `distortion`
-(include/lab4d_distort.h, csrc/distort.hip) is the distortion loss of such a list per ray, with its adjoint.  Nothing here synchronises
+(include/lab4d_distort.h, csrc/distort.hip) is the distortion loss of such a list per ray, with its adjoint.  `merge` and `merge_rows`
+(include/lab4d_pmerge.h, csrc/pmerge.hip) z-sort the rows of two such lists of the same rays into one and gather per-row values through the
+order: a foreground field in front of a background, composited as one list.  Nothing here synchronises
 with the host: every call can be captured in a hipGraph."""
 import math
 import struct
@@ -261,3 +263,111 @@ def distortion(density, deltas, mid, width, rays):
     if rs.dtype != torch.int32 or rc.dtype != torch.int32 or rs.ndim != 1 or rs.shape != rc.shape:
         raise RuntimeError("lab4d_amd.packed.distortion: ray_start / ray_count must be int32 (R,)")
     return _PackedDistortion.apply(density.reshape(P), deltas.reshape(P), mid.detach().reshape(P), width.detach().reshape(P), rs, rc)
+
+
+# ---------------------------------------------------------------------------------------------------
+# merge of two packed lists per ray by depth (include/lab4d_pmerge.h, csrc/pmerge.hip)
+# ---------------------------------------------------------------------------------------------------
+class MergedRays:
+    """The packed list of one merge: per row (cap rows) t, deltas (copied bit for bit from the source row), ray_idx int32, src int32 = the
+    source row in the concatenation [A | B] (i for A's row i, Pa + i for B's row i; -1 in the parked rows).  pos_a (Pa,), pos_b (Pb,) int32:
+    the merged row every input row went to, -1 for a row that no ray owns or that fell behind the capacity.  Per ray (R): ray_start,
+    ray_count int32 as in a PackedRays; total, overflow likewise.  No xyz / dirs: the two lists may live in different frames."""
+    __slots__ = ("t", "deltas", "ray_idx", "src", "pos_a", "pos_b", "ray_start", "ray_count", "total", "overflow", "R", "cap", "Pa", "Pb")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    @property
+    def from_b(self):
+        """(cap,) bool: the row came from list B (False in the parked rows)"""
+        return self.src >= self.Pa
+
+
+def _merge_list(name, rays):
+    t, deltas, rs, rc = rays.t, rays.deltas, rays.ray_start, rays.ray_count
+    for k, x in (("t", t), ("deltas", deltas)):
+        if x.dtype != torch.float32 or x.ndim != 1:
+            raise RuntimeError("lab4d_amd.packed.merge: %s.%s must be float32 (n), got %s %s" % (name, k, x.dtype, tuple(x.shape)))
+    if deltas.shape[0] != t.shape[0]:
+        raise RuntimeError("lab4d_amd.packed.merge: %s.t and %s.deltas disagree on the number of rows" % (name, name))
+    if rs.dtype != torch.int32 or rc.dtype != torch.int32 or rs.ndim != 1 or rs.shape != rc.shape:
+        raise RuntimeError("lab4d_amd.packed.merge: %s.ray_start / ray_count must be int32 (R,)" % name)
+    return t, deltas, rs, rc
+
+
+@torch.no_grad()
+def merge(rays_a, rays_b, cap=None):
+    """rays_a, rays_b: two packed lists of the SAME rays -- anything with t, deltas, ray_start, ray_count (a PackedRays, a PrunedRays, a
+    MergedRays: three fields merge by merging twice) -- each non-decreasing in t within every ray, as march and prune emit them, with t in
+    the same units along the same ray (the lists may have been marched in different frames).  -> MergedRays with `cap` rows (default: the
+    rows of both lists, rays_a.cap + rays_b.cap, so that nothing can overflow): per ray the stable z-sort of the concatenation, a tie
+    between the lists going to A (rules: include/lab4d_pmerge.h; what MultiFields.compose_fields does on the dense layout).  Two calls
+    (count, write) around one prefix sum; no read-back."""
+    t_a, d_a, rs_a, rc_a = _merge_list("rays_a", rays_a)
+    t_b, d_b, rs_b, rc_b = _merge_list("rays_b", rays_b)
+    if rs_a.shape != rs_b.shape:
+        raise RuntimeError("lab4d_amd.packed.merge: the lists disagree on the number of rays: %d and %d" % (rs_a.shape[0], rs_b.shape[0]))
+    Pa, Pb, R = t_a.shape[0], t_b.shape[0], rs_a.shape[0]
+    if Pa + Pb >= 1 << 31:
+        raise RuntimeError("lab4d_amd.packed.merge: Pa + Pb = %d + %d does not fit 31 bits" % (Pa, Pb))
+    cap = Pa + Pb if cap is None else int(cap)
+    if not 0 <= cap < 1 << 31:
+        raise RuntimeError("lab4d_amd.packed.merge: cap = %d outside [0, 2^31)" % cap)
+    _lib.require_device(t_a, d_a, rs_a, rc_a, t_b, d_b, rs_b, rc_b)
+    dev = t_a.device
+    count = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.call("packed_merge_count", rs_a, rc_a, Pa, rs_b, rc_b, Pb, R, count)
+    start = torch.cumsum(count, 0, dtype=torch.int32) - count  # (the exclusive scan: at most Pa + Pb < 2^31 rows)
+    out = {"t": torch.empty(cap, device=dev), "deltas": torch.empty(cap, device=dev), "ray_idx": torch.empty(cap, dtype=torch.int32, device=dev),
+           "src": torch.empty(cap, dtype=torch.int32, device=dev), "pos_a": torch.empty(Pa, dtype=torch.int32, device=dev),
+           "pos_b": torch.empty(Pb, dtype=torch.int32, device=dev), "ray_count": torch.empty(R, dtype=torch.int32, device=dev),
+           "total": torch.empty(1, dtype=torch.int32, device=dev)}
+    overflow = torch.empty(1, dtype=torch.uint8, device=dev)
+    _lib.call("packed_merge_write", t_a.detach(), d_a.detach(), rs_a, rc_a, Pa, t_b.detach(), d_b.detach(), rs_b, rc_b, Pb, R, start, cap, out["t"], out["deltas"],
+              out["ray_idx"], out["src"], out["pos_a"], out["pos_b"], out["ray_count"], out["total"], overflow)
+    return MergedRays(ray_start=start, overflow=overflow.view(torch.bool), R=R, cap=cap, Pa=Pa, Pb=Pb, **out)
+
+
+class _MergeRows(Function):
+    @staticmethod
+    def forward(ctx, a, b, src, pos_a, pos_b, C):
+        cap, Pa, Pb = src.shape[0], pos_a.shape[0], pos_b.shape[0]
+        out = torch.empty(cap, C, device=src.device)
+        _lib.call("packed_merge_gather", a, Pa, b, Pb, src, cap, C, out)
+        ctx.save_for_backward(pos_a, pos_b)
+        ctx.C = C
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        pos_a, pos_b = ctx.saved_tensors
+        g_out, grads = g_out.contiguous(), []
+        for need, pos in zip(ctx.needs_input_grad[:2], (pos_a, pos_b)):  # the adjoint of a part: the same gather, through the inverse
+            g = torch.empty(pos.shape[0], ctx.C, device=g_out.device) if need else None
+            if need:
+                _lib.call("packed_merge_gather", g_out, g_out.shape[0], None, 0, pos, pos.shape[0], ctx.C, g)
+            grads.append(g)
+        return (*grads, None, None, None, None)
+
+
+def merge_rows(merged, a=None, b=None):
+    """Per-row values of the two merged lists in the merged order: a float32 (Pa,) or (Pa, C), b float32 (Pb,) or (Pb, C), 1 <= C <= 64;
+    None stands for a block of zeros (a key that only one field produces), both None is an error.  -> (cap,) or (cap, C): row j holds
+    a[src[j]], b[src[j] - Pa], or zeros in a parked row.  Differentiable in a and b: the adjoint is the same gather through pos_a / pos_b
+    (every value is a copy, so it is the exact transpose)."""
+    if a is None and b is None:
+        raise RuntimeError("lab4d_amd.packed.merge_rows: a and b are both None")
+    ref = a if a is not None else b
+    for name, x, n in (("a", a, merged.Pa), ("b", b, merged.Pb)):
+        if x is not None and (x.dtype != torch.float32 or x.ndim not in (1, 2) or x.shape[0] != n or x.shape[1:] != ref.shape[1:]):
+            raise RuntimeError("lab4d_amd.packed.merge_rows: %s must be float32 (%d,) or (%d, 1..64) with the channels of the other part, got %s %s"
+                               % (name, n, n, x.dtype, tuple(x.shape)))
+    C = 1 if ref.ndim == 1 else ref.shape[1]
+    if not 1 <= C <= 64:
+        raise RuntimeError("lab4d_amd.packed.merge_rows: %d channels outside [1, 64]" % C)
+    _lib.require_device(a, b, merged.src, merged.pos_a, merged.pos_b)
+    out = _MergeRows.apply(None if a is None else a.reshape(-1, C), None if b is None else b.reshape(-1, C), merged.src, merged.pos_a, merged.pos_b, C)
+    return out[:, 0] if ref.ndim == 1 else out
