@@ -326,6 +326,13 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_pmerge.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 22. Importance resampling of a packed sample list per ray: the compositing weights of the list and its inverse-CDF resampling into
+ *     n_imp rows per ray, 2's lab4d_sample_pdf for the packed layout -- nnutils/nerf.py:686-738 (NeRF.importance_sampling),
+ *     utils/render_utils.py:187-233 (sample_pdf).  See lab4d_presample.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_presample.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,9 @@ fixed step through the occupied cells only (packed.march), the field runs on the
 differentiable field runs: density() of the kept rows without gradients, packed.prune by transmittance and opacity, forward() on the survivors
 (include/lab4d_prune.h).  with_distortion=True on either adds the distortion loss of the list per ray (include/lab4d_distort.h).
 render_packed_pair() composites TWO hash fields, an object in front of a scene, into one image: each is marched through its own grid and the two
-packed lists are z-merged per ray (include/lab4d_pmerge.h).  All of it is opt-in.
+packed lists are z-merged per ray (include/lab4d_pmerge.h).  render_packed_resampled() renders coarse-to-fine: a march at a coarse step, the
+weights of that list without gradients, and the differentiable field on n_imp rows per ray resampled by inverse CDF where the weights are
+(include/lab4d_presample.h).  All of it is opt-in.
 
 The SDF as an SDF: sdf_gradient() returns the sdf with its gradient in the point from one fused kernel (hashsdf.py, include/lab4d_hashsdf.h),
 differentiable in the table and the geometry net; eikonal_loss() and normals() build on it (the counterparts of nnutils/nerf.py:416-493), and
@@ -241,6 +243,24 @@ def render_packed_pruned(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.P
     if with_normal:
         out += (rendered["normal"],)
     return out + (_packed_distortion(dens_s, kept, dt),) if with_distortion else out
+
+
+def render_packed_resampled(P, cfg, grid, origin, dir, t_range, dt, cap, n_imp, fine_cap=None, u=None, eps=1e-5, prec=mlp.PREC_F32, table_grad_f16=False,
+                            k_max=1024, res=None):
+    """render_packed() coarse-to-fine (include/lab4d_presample.h), the reference's importance sampling (nnutils/nerf.py:686-738) on packed
+    lists: packed.march at the COARSE step dt; density() of the marched rows under no_grad; packed.weights turns it into the compositing
+    weights of the coarse list; packed.resample places n_imp new rows per ray where those weights are (u, eps: see there; at most fine_cap
+    rows, default R * n_imp: no overflow; STATIC like cap); forward() runs on the new rows ONLY and packed.composite renders them with
+    depth = t.  The sample positions are detached, as the reference detaches them; gradients reach the table, the Linears and logibeta.
+    A ray without marched rows, or whose rows weigh nothing with eps = 0, renders zeros.  Returns (rgb (R,3), mask (R,1), depth (R,1),
+    total, overflow (the march's), total_fine (1,) int32 = the resampled rows before fine_cap, overflow_fine (1,) bool)."""
+    rays = packed.march(grid, origin, dir, t_range, dt, cap, k_max=k_max)
+    with torch.no_grad():
+        dens0 = density(P, cfg, rays.xyz, prec=prec, res=res)
+        fine = packed.resample(rays, packed.weights(dens0, rays.deltas, rays), origin, dir, n_imp, aabb=grid.aabb, u=u, eps=eps, cap=fine_cap)
+    rgb_s, dens_s = forward(P, cfg, fine.xyz, fine.dirs, spf=max(fine.cap, 1), prec=prec, res=res, table_grad_f16=table_grad_f16)
+    rendered, mask = packed.composite(dens_s, fine.deltas, {"rgb": rgb_s, "depth": fine.t[:, None]}, fine)
+    return rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow, fine.total, fine.overflow
 
 
 PackedField = collections.namedtuple("PackedField", "P cfg grid origin dir t_range dt cap")

@@ -6,7 +6,9 @@ csrc/prune.hip) drops the rows of such a list that lie behind the point where th
 given the density of the rows: the step between a density pass without gradients and the differentiable field.  `distortion`
 (include/lab4d_distort.h, csrc/distort.hip) is the distortion loss of such a list per ray, with its adjoint.  `merge` and `merge_rows`
 (include/lab4d_pmerge.h, csrc/pmerge.hip) z-sort the rows of two such lists of the same rays into one and gather per-row values through the
-order: a foreground field in front of a background, composited as one list.  Nothing here synchronises
+order: a foreground field in front of a background, composited as one list.  `weights` and `resample`
+(include/lab4d_presample.h, csrc/presample.hip) are the coarse-to-fine step: the compositing weights of a list without gradients, and the
+inverse-CDF resampling of the list into n_imp rows per ray where those weights are.  Nothing here synchronises
 with the host: every call can be captured in a hipGraph."""
 import math
 import struct
@@ -371,3 +373,89 @@ def merge_rows(merged, a=None, b=None):
     _lib.require_device(a, b, merged.src, merged.pos_a, merged.pos_b)
     out = _MergeRows.apply(None if a is None else a.reshape(-1, C), None if b is None else b.reshape(-1, C), merged.src, merged.pos_a, merged.pos_b, C)
     return out[:, 0] if ref.ndim == 1 else out
+
+
+# ---------------------------------------------------------------------------------------------------
+# importance resampling of a packed list per ray (include/lab4d_presample.h, csrc/presample.hip)
+# ---------------------------------------------------------------------------------------------------
+def _ray_table(where, rays):
+    rs, rc = rays.ray_start, rays.ray_count
+    if rs.dtype != torch.int32 or rc.dtype != torch.int32 or rs.ndim != 1 or rs.shape != rc.shape:
+        raise RuntimeError("lab4d_amd.packed.%s: ray_start / ray_count must be int32 (R,)" % where)
+    return rs, rc
+
+
+@torch.no_grad()
+def weights(density, deltas, rays, with_trans=False):
+    """The compositing weights of a packed list, the reference's compute_weights (utils/render_utils.py:99-131) per ray of its own length:
+    density, deltas float32 (P,) or (P,1) on the rows of `rays` (a PackedRays, PrunedRays or MergedRays, or anything with ray_start /
+    ray_count (R,) int32) -> w (P,): w_i = (1 - exp(-tau_i)) exp(-sum of tau before row i), tau = density * deltas with NaN or a value not
+    > 0 counting as 0 (rules: include/lab4d_presample.h); zeros in the rows that no ray owns.  with_trans=True: -> (w, trans (R,)), the
+    transmittance behind a ray's last row, 1 for a ray without rows.  No gradients: what `resample` places its rows by."""
+    rs, rc = _ray_table("weights", rays)
+    P, R = density.shape[0], rs.shape[0]
+    for name, x in (("density", density), ("deltas", deltas)):
+        if x.numel() != P or x.dtype != torch.float32 or x.ndim not in (1, 2):
+            raise RuntimeError("lab4d_amd.packed.weights: %s must be float32 (%d,) or (%d, 1), got %s %s" % (name, P, P, x.dtype, tuple(x.shape)))
+    if not (P < 1 << 31 and R < 1 << 31):
+        raise RuntimeError("lab4d_amd.packed.weights: P = %d or R = %d does not fit 31 bits" % (P, R))
+    _lib.require_device(density, deltas, rs, rc)
+    w = torch.zeros(P, device=density.device)  # (zeros: the rows that no ray owns are not written)
+    trans = torch.empty(R, device=density.device) if with_trans else None
+    _lib.call("packed_weights", density.detach().reshape(P), deltas.detach().reshape(P), rs, rc, R, P, w, trans)
+    return (w, trans) if with_trans else w
+
+
+@torch.no_grad()
+def resample(rays, weights, origin, dir, n_imp, *, aabb, u=None, eps=1e-5, cap=None):
+    """Inverse-CDF resampling of a packed list into n_imp rows per ray, the reference's importance sampling (nnutils/nerf.py:686-738 with
+    render_utils.sample_pdf) for rays of their own lengths.  rays: a PackedRays, a PrunedRays or a MergedRays (t, deltas, ray_start,
+    ray_count); weights float32 (P,) or (P,1) on its rows (`weights` above; detached: the placement is not differentiable); origin, dir
+    (R,3), the rays the list was marched along; aabb: the box (2,3) / (6,) float32 of the park point (grid.aabb); u: None for the stratified
+    centres (k + 0.5) / n_imp, or float32 (R, n_imp) in [0, 1], non-decreasing per ray; eps >= 0 is added to every weight, as sample_pdf
+    adds it.  A row of mass m_i = max(w_i, 0) + eps is an interval deltas_i / |dir| wide around t_i that carries m_i evenly; sample k lies
+    where the ray's cumulative mass reaches u_k of its total, deltas = the length that carries 1 / n_imp of the mass, at most the source
+    row's own (rules: include/lab4d_presample.h).  A ray without rows or without mass emits nothing, every other ray n_imp rows in
+    ascending t.  -> PrunedRays with `cap` rows (default R * n_imp: it cannot overflow), src_row = the source row of every new row.  Two
+    calls (count, write) around one prefix sum; no read-back."""
+    t, deltas = rays.t, rays.deltas
+    rs, rc = _ray_table("resample", rays)
+    for name, x, tail in (("rays.t", t, ()), ("rays.deltas", deltas, ()), ("origin", origin, (3,)), ("dir", dir, (3,))):
+        if x.dtype != torch.float32 or x.ndim != len(tail) + 1 or tuple(x.shape[1:]) != tail:
+            raise RuntimeError("lab4d_amd.packed.resample: %s must be float32 (n%s), got %s %s" % (name, "".join(", %d" % c for c in tail), x.dtype, tuple(x.shape)))
+    P, R, n_imp, eps = t.shape[0], rs.shape[0], int(n_imp), float(eps)
+    if deltas.shape[0] != P:
+        raise RuntimeError("lab4d_amd.packed.resample: rays.t and rays.deltas disagree on the number of rows")
+    if weights.numel() != P or weights.dtype != torch.float32 or weights.ndim not in (1, 2):
+        raise RuntimeError("lab4d_amd.packed.resample: weights must be float32 (%d,) or (%d, 1), got %s %s" % (P, P, weights.dtype, tuple(weights.shape)))
+    if origin.shape[0] != R or dir.shape[0] != R:
+        raise RuntimeError("lab4d_amd.packed.resample: origin %s and dir %s disagree with the list's %d rays" % (tuple(origin.shape), tuple(dir.shape), R))
+    if aabb.numel() != 6 or aabb.dtype != torch.float32:
+        raise RuntimeError("lab4d_amd.packed.resample: aabb must be float32 (2, 3) or (6,), got %s %s" % (aabb.dtype, tuple(aabb.shape)))
+    if n_imp < 1:
+        raise RuntimeError("lab4d_amd.packed.resample: n_imp = %d must be >= 1" % n_imp)
+    if not (P < 1 << 31 and R * n_imp < 1 << 31):
+        raise RuntimeError("lab4d_amd.packed.resample: P = %d or R * n_imp = %d * %d does not fit 31 bits" % (P, R, n_imp))
+    if not (math.isfinite(eps) and eps >= 0):
+        raise RuntimeError("lab4d_amd.packed.resample: eps = %r must be finite and >= 0" % eps)
+    if u is not None and (u.dtype != torch.float32 or tuple(u.shape) != (R, n_imp)):
+        raise RuntimeError("lab4d_amd.packed.resample: u must be float32 (%d, %d), got %s %s" % (R, n_imp, u.dtype, tuple(u.shape)))
+    cap = R * n_imp if cap is None else int(cap)
+    if not 0 <= cap < 1 << 31:
+        raise RuntimeError("lab4d_amd.packed.resample: cap = %d outside [0, 2^31)" % cap)
+    _lib.require_device(t, deltas, rs, rc, weights, origin, dir, aabb, u)
+    dev = t.device
+    weights, t, deltas, origin, dir = weights.detach().reshape(P), t.detach(), deltas.detach(), origin.detach(), dir.detach()
+    cdf = torch.zeros(P, device=dev)  # (zeros: the rows that no ray owns are not written)
+    mass = torch.empty(R, device=dev)
+    count = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.call("packed_resample_count", weights, rs, rc, R, P, n_imp, eps, cdf, mass, count)
+    start = torch.cumsum(count, 0, dtype=torch.int32) - count  # (the exclusive scan: at most R * n_imp < 2^31 rows)
+    out = {"t": torch.empty(cap, device=dev), "deltas": torch.empty(cap, device=dev), "xyz": torch.empty(cap, 3, device=dev),
+           "dirs": torch.empty(cap, 3, device=dev), "ray_idx": torch.empty(cap, dtype=torch.int32, device=dev),
+           "src_row": torch.empty(cap, dtype=torch.int32, device=dev), "ray_count": torch.empty(R, dtype=torch.int32, device=dev),
+           "total": torch.empty(1, dtype=torch.int32, device=dev)}
+    overflow = torch.empty(1, dtype=torch.uint8, device=dev)
+    _lib.call("packed_resample_write", weights, cdf, mass, t, deltas, rs, rc, start, R, P, origin, dir, None if u is None else u.detach(), n_imp, eps, cap, aabb,
+              out["t"], out["deltas"], out["xyz"], out["dirs"], out["ray_idx"], out["src_row"], out["ray_count"], out["total"], overflow)
+    return PrunedRays(ray_start=start, overflow=overflow.view(torch.bool), R=R, cap=cap, **out)
