@@ -333,6 +333,13 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_presample.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 23. Proposal (interval) loss between two packed sample lists per ray, forward and adjoint, and the adjoint of 22's compositing
+ *     weights: what a trained proposal field needs -- Barron et al. 2022 (mip-NeRF 360), not in the reference, parity unpinned.
+ *     See lab4d_proposal.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_proposal.h"
+
 #ifdef __cplusplus
 }
 #endif

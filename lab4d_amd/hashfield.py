@@ -21,7 +21,8 @@ differentiable field runs: density() of the kept rows without gradients, packed.
 render_packed_pair() composites TWO hash fields, an object in front of a scene, into one image: each is marched through its own grid and the two
 packed lists are z-merged per ray (include/lab4d_pmerge.h).  render_packed_resampled() renders coarse-to-fine: a march at a coarse step, the
 weights of that list without gradients, and the differentiable field on n_imp rows per ray resampled by inverse CDF where the weights are
-(include/lab4d_presample.h).  All of it is opt-in.
+(include/lab4d_presample.h).  render_packed_proposal() takes those weights from a second, cheaper hash field instead and returns the interval loss
+that trains it (include/lab4d_proposal.h).  All of it is opt-in.
 
 The SDF as an SDF: sdf_gradient() returns the sdf with its gradient in the point from one fused kernel (hashsdf.py, include/lab4d_hashsdf.h),
 differentiable in the table and the geometry net; eikonal_loss() and normals() build on it (the counterparts of nnutils/nerf.py:416-493), and
@@ -261,6 +262,28 @@ def render_packed_resampled(P, cfg, grid, origin, dir, t_range, dt, cap, n_imp, 
     rgb_s, dens_s = forward(P, cfg, fine.xyz, fine.dirs, spf=max(fine.cap, 1), prec=prec, res=res, table_grad_f16=table_grad_f16)
     rendered, mask = packed.composite(dens_s, fine.deltas, {"rgb": rgb_s, "depth": fine.t[:, None]}, fine)
     return rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow, fine.total, fine.overflow
+
+
+def render_packed_proposal(Pp, cfgp, P, cfg, grid, origin, dir, t_range, dt, cap, n_imp, fine_cap=None, u=None, eps=1e-5, prec=mlp.PREC_F32,
+                           table_grad_f16=False, k_max=1024, res=None, resp=None, loss_eps=torch.finfo(torch.float32).eps):
+    """render_packed_resampled() with a TRAINED proposal field (include/lab4d_proposal.h), the scheme of Barron et al. 2022 (mip-NeRF 360):
+    the coarse pass runs a second, cheaper hash field (Pp, cfgp: a small table) instead of the main one.  packed.march at the step dt;
+    density(Pp, cfgp) of the marched rows WITH gradients; packed.render_weights turns it into the weights of the coarse list;
+    packed.resample places n_imp rows per ray by the detached weights (u, eps, fine_cap: see render_packed_resampled); forward(P, cfg) runs
+    on the new rows and packed.composite renders them; packed.weights of the fine list under no_grad; packed.proposal_loss (loss_eps) holds
+    the coarse weights above the fine ones.  Returns render_packed_resampled's tuple with prop_loss (R,1) appended.  The image's gradients
+    reach P only (the sample positions are detached), the loss's gradients reach Pp only (the fine weights are detached): one backward of
+    image loss + prop_loss.mean() trains both.  res / resp: the level resolutions of cfg / cfgp."""
+    rays = packed.march(grid, origin, dir, t_range, dt, cap, k_max=k_max)
+    dens_p = density(Pp, cfgp, rays.xyz, prec=prec, res=resp)
+    w_p = packed.render_weights(dens_p, rays.deltas, rays)
+    fine = packed.resample(rays, w_p.detach(), origin, dir, n_imp, aabb=grid.aabb, u=u, eps=eps, cap=fine_cap)
+    rgb_s, dens_s = forward(P, cfg, fine.xyz, fine.dirs, spf=max(fine.cap, 1), prec=prec, res=res, table_grad_f16=table_grad_f16)
+    rendered, mask = packed.composite(dens_s, fine.deltas, {"rgb": rgb_s, "depth": fine.t[:, None]}, fine)
+    with torch.no_grad():
+        w_f = packed.weights(dens_s, fine.deltas, fine)
+    prop_loss = packed.proposal_loss(rays, w_p, fine, w_f, dir, eps=loss_eps)[:, None]
+    return rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow, fine.total, fine.overflow, prop_loss
 
 
 PackedField = collections.namedtuple("PackedField", "P cfg grid origin dir t_range dt cap")

@@ -8,8 +8,11 @@ given the density of the rows: the step between a density pass without gradients
 (include/lab4d_pmerge.h, csrc/pmerge.hip) z-sort the rows of two such lists of the same rays into one and gather per-row values through the
 order: a foreground field in front of a background, composited as one list.  `weights` and `resample`
 (include/lab4d_presample.h, csrc/presample.hip) are the coarse-to-fine step: the compositing weights of a list without gradients, and the
-inverse-CDF resampling of the list into n_imp rows per ray where those weights are.  Nothing here synchronises
+inverse-CDF resampling of the list into n_imp rows per ray where those weights are.  `render_weights` and `proposal_loss`
+(include/lab4d_proposal.h, csrc/proposal.hip) train a proposal field for that step: the weights with a backward, and the interval loss
+that makes a proposal list's weights an upper envelope of the fine list's.  Nothing here synchronises
 with the host: every call can be captured in a hipGraph."""
+import collections
 import math
 import struct
 
@@ -459,3 +462,104 @@ def resample(rays, weights, origin, dir, n_imp, *, aabb, u=None, eps=1e-5, cap=N
     _lib.call("packed_resample_write", weights, cdf, mass, t, deltas, rs, rc, start, R, P, origin, dir, None if u is None else u.detach(), n_imp, eps, cap, aabb,
               out["t"], out["deltas"], out["xyz"], out["dirs"], out["ray_idx"], out["src_row"], out["ray_count"], out["total"], overflow)
     return PrunedRays(ray_start=start, overflow=overflow.view(torch.bool), R=R, cap=cap, **out)
+
+
+# ---------------------------------------------------------------------------------------------------
+# proposal loss between two packed lists, and differentiable weights (include/lab4d_proposal.h, csrc/proposal.hip)
+# ---------------------------------------------------------------------------------------------------
+_RayTable = collections.namedtuple("_RayTable", "ray_start ray_count")
+
+
+class _RenderWeights(Function):
+    @staticmethod
+    def forward(ctx, density, deltas, ray_start, ray_count):
+        w, trans = weights(density, deltas, _RayTable(ray_start, ray_count), with_trans=True)  # (the forward IS `weights`: one launch site)
+        ctx.save_for_backward(density, deltas, ray_start, ray_count)
+        return w, trans
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_w, g_trans):
+        density, deltas, ray_start, ray_count = ctx.saved_tensors
+        P, R = density.shape[0], ray_start.shape[0]
+        g_density = torch.zeros_like(density)
+        _lib.call("packed_weights_backward", density, deltas, ray_start, ray_count, R, P, g_w.contiguous(), g_trans.contiguous(), g_density)
+        return g_density, None, None, None
+
+
+def render_weights(density, deltas, rays, with_trans=False):
+    """`weights` with a backward: the compositing weights w (P,) of a packed list (and trans (R,) with with_trans=True), differentiable
+    (once) in density -- what a proposal field is trained through (`proposal_loss`).  density, deltas float32 (P,) or (P,1) on the rows of
+    `rays`; deltas is detached.  The adjoint recomputes tau, E and w (rules: include/lab4d_proposal.h, WEIGHTS ADJOINT); a row whose tau
+    counted as 0 gets no gradient.  `weights` stays the call for a pass without gradients."""
+    rs, rc = _ray_table("render_weights", rays)
+    P, R = density.shape[0], rs.shape[0]
+    for name, x in (("density", density), ("deltas", deltas)):
+        if x.numel() != P or x.dtype != torch.float32 or x.ndim not in (1, 2):
+            raise RuntimeError("lab4d_amd.packed.render_weights: %s must be float32 (%d,) or (%d, 1), got %s %s" % (name, P, P, x.dtype, tuple(x.shape)))
+    if not (P < 1 << 31 and R < 1 << 31):
+        raise RuntimeError("lab4d_amd.packed.render_weights: P = %d or R = %d does not fit 31 bits" % (P, R))
+    _lib.require_device(density, deltas, rs, rc)
+    w, trans = _RenderWeights.apply(density.reshape(P), deltas.detach().reshape(P), rs, rc)
+    return (w, trans) if with_trans else w
+
+
+class _ProposalLoss(Function):
+    @staticmethod
+    def forward(ctx, w_e, t_e, deltas_e, rs_e, rc_e, w_f, t_f, deltas_f, rs_f, rc_f, dir, eps):
+        Pe, Pf, R, dev = w_e.shape[0], w_f.shape[0], rs_e.shape[0], w_e.device
+        lo, hi, cdf = torch.zeros(Pe, device=dev), torch.zeros(Pe, device=dev), torch.zeros(Pe, device=dev)  # (zeros: the rows of no ray are not written)
+        _lib.call("packed_envelope", w_e, t_e, deltas_e, rs_e, rc_e, dir, R, Pe, lo, hi, cdf)
+        span, coef = torch.zeros(Pf, 2, dtype=torch.int32, device=dev), torch.zeros(Pf, device=dev)
+        loss = torch.zeros(R, device=dev)
+        _lib.call("packed_proposal_forward", lo, hi, cdf, rs_e, rc_e, Pe, w_f, t_f, deltas_f, rs_f, rc_f, Pf, dir, R, eps, span, coef, loss)
+        ctx.save_for_backward(span, coef, w_e, rs_e, rc_e, rs_f, rc_f)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss):
+        span, coef, w_e, rs_e, rc_e, rs_f, rc_f = ctx.saved_tensors
+        g_w_e = torch.zeros_like(w_e)
+        _lib.call("packed_proposal_backward", g_loss.contiguous(), span, coef, w_e, rs_e, rc_e, w_e.shape[0], rs_f, rc_f, coef.shape[0], rs_e.shape[0], g_w_e)
+        return (g_w_e,) + (None,) * 11
+
+
+def proposal_loss(rays_env, w_env, rays_fine, w_fine, dir, eps=torch.finfo(torch.float32).eps):
+    """The proposal (interval) loss of Barron et al. 2022 (mip-NeRF 360, equation 13) per ray between two packed lists of the SAME rays
+    (rules: include/lab4d_proposal.h).  rays_env: the proposal's list (t, deltas, ray_start, ray_count: a PackedRays or a PrunedRays, lo and
+    hi non-decreasing per ray as march and prune emit them) with weights w_env float32 (Pe,) or (Pe,1); rays_fine: the fine list (any
+    order of intervals, e.g. a resampled list) with weights w_fine (Pf,) or (Pf,1); dir (R,3) the rays both were marched along.  A row is
+    the interval deltas / |dir| wide around t.  B_i = the summed weight of the envelope rows that overlap fine row i;
+    loss[r] = sum_i max(w_fine_i - B_i, 0)^2 / (w_fine_i + eps).  -> (R,), 0 for a ray without fine rows.  Differentiable (once) in w_env
+    only: w_fine is detached, as mip-NeRF 360 stops it.  Three calls (envelope, forward; backward); no read-back, no atomics."""
+    eps = float(eps)
+    lists = []
+    for name, rays, w in (("rays_env", rays_env, w_env), ("rays_fine", rays_fine, w_fine)):
+        t, deltas = rays.t, rays.deltas
+        rs, rc = _ray_table("proposal_loss", rays)
+        for k, x in ((name + ".t", t), (name + ".deltas", deltas)):
+            if x.dtype != torch.float32 or x.ndim != 1:
+                raise RuntimeError("lab4d_amd.packed.proposal_loss: %s must be float32 (n), got %s %s" % (k, x.dtype, tuple(x.shape)))
+        P = t.shape[0]
+        if deltas.shape[0] != P:
+            raise RuntimeError("lab4d_amd.packed.proposal_loss: %s.t and %s.deltas disagree on the number of rows" % (name, name))
+        wname = "w_env" if name == "rays_env" else "w_fine"
+        if w.numel() != P or w.dtype != torch.float32 or w.ndim not in (1, 2):
+            raise RuntimeError("lab4d_amd.packed.proposal_loss: %s must be float32 (%d,) or (%d, 1), got %s %s" % (wname, P, P, w.dtype, tuple(w.shape)))
+        lists.append((w, t, deltas, rs, rc, P))
+    (w_e, t_e, d_e, rs_e, rc_e, Pe), (w_f, t_f, d_f, rs_f, rc_f, Pf) = lists
+    R = rs_e.shape[0]
+    if rs_f.shape[0] != R:
+        raise RuntimeError("lab4d_amd.packed.proposal_loss: the lists disagree on the number of rays: %d and %d" % (R, rs_f.shape[0]))
+    if dir.dtype != torch.float32 or dir.ndim != 2 or dir.shape[1] != 3:
+        raise RuntimeError("lab4d_amd.packed.proposal_loss: dir must be float32 (n, 3), got %s %s" % (dir.dtype, tuple(dir.shape)))
+    if dir.shape[0] != R:
+        raise RuntimeError("lab4d_amd.packed.proposal_loss: dir %s disagrees with the lists' %d rays" % (tuple(dir.shape), R))
+    if not (Pe < 1 << 31 and Pf < 1 << 31 and R < 1 << 31):
+        raise RuntimeError("lab4d_amd.packed.proposal_loss: Pe = %d, Pf = %d or R = %d does not fit 31 bits" % (Pe, Pf, R))
+    if not (math.isfinite(eps) and eps >= 0):
+        raise RuntimeError("lab4d_amd.packed.proposal_loss: eps = %r must be finite and >= 0" % eps)
+    _lib.require_device(w_e, t_e, d_e, rs_e, rc_e, w_f, t_f, d_f, rs_f, rc_f, dir)
+    return _ProposalLoss.apply(w_e.reshape(Pe), t_e.detach(), d_e.detach(), rs_e, rc_e, w_f.detach().reshape(Pf), t_f.detach(), d_f.detach(), rs_f, rc_f,
+                               dir.detach(), eps)
