@@ -340,6 +340,12 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_proposal.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 24. Cascaded occupancy grids and cone-stepped packed marching: 12 and 13 for a scene box many times as wide as the object -- Mueller
+ *     et al. 2022, appendix E; not in the reference, parity unpinned.  See lab4d_conemarch.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_conemarch.h"
+
 #ifdef __cplusplus
 }
 #endif

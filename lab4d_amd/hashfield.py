@@ -22,7 +22,9 @@ render_packed_pair() composites TWO hash fields, an object in front of a scene, 
 packed lists are z-merged per ray (include/lab4d_pmerge.h).  render_packed_resampled() renders coarse-to-fine: a march at a coarse step, the
 weights of that list without gradients, and the differentiable field on n_imp rows per ray resampled by inverse CDF where the weights are
 (include/lab4d_presample.h).  render_packed_proposal() takes those weights from a second, cheaper hash field instead and returns the interval loss
-that trains it (include/lab4d_proposal.h).  All of it is opt-in.
+that trains it (include/lab4d_proposal.h).  render_packed_cone() is render_packed() for a scene box many times as wide as the object: the step
+grows with the distance and every sample is looked up in a cascade of occupancy grids (occgrid.OccupancyCascade, refreshed with
+update_occupancy_cascade(); include/lab4d_conemarch.h).  All of it is opt-in.
 
 The SDF as an SDF: sdf_gradient() returns the sdf with its gradient in the point from one fused kernel (hashsdf.py, include/lab4d_hashsdf.h),
 differentiable in the table and the geometry net; eikonal_loss() and normals() build on it (the counterparts of nnutils/nerf.py:416-493), and
@@ -202,6 +204,49 @@ def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32
     if with_normal:
         out += (rendered["normal"],)
     return out + (_packed_distortion(dens_s, rays, dt),) if with_distortion else out
+
+
+@torch.no_grad()
+def update_occupancy_cascade(P, cfg, cascade, prec=mlp.PREC_F32, chunk=1 << 22):
+    """Refreshes an occgrid.OccupancyCascade from the field: the density at every level's cell centres through forward() (in pieces of
+    `chunk` points), then cascade.update -- the propagation from fine to coarse, then ema = max(ema * decay, density), bit = ema > thresh
+    per level.  The field lives on the OUTERMOST box, as in the paper: P["aabb"] must equal cascade.aabbs[K - 1], which is checked first
+    (the one read-back of this call) and raises otherwise.  Returns the cascade."""
+    outer = cascade.aabbs[cascade.K - 1]
+    box = P["aabb"]
+    if box.numel() != 6 or not torch.equal(box.detach().reshape(6).to(device=outer.device, dtype=torch.float32), outer):
+        raise RuntimeError("hashfield.update_occupancy_cascade: P[\"aabb\"] must be the cascade's outermost box aabbs[K - 1] = %s, got %s"
+                           % (outer.tolist(), box.reshape(-1).tolist()))
+    pts = cascade.cell_centers().reshape(-1, 3)
+    dens = torch.empty(pts.shape[0], dtype=torch.float32, device=pts.device)
+    res = resolutions(cfg, pts.device)
+    for o in range(0, pts.shape[0], chunk):
+        x = pts[o:o + chunk]
+        d = torch.zeros_like(x)
+        d[:, 2] = 1.0
+        dens[o:o + chunk] = forward(P, cfg, x, d, spf=x.shape[0], prec=prec, res=res)[1][:, 0]
+    return cascade.update(dens.reshape(cascade.K, -1))
+
+
+def render_packed_cone(P, cfg, cascade, origin, dir, t_range, cone, dt_min, dt_max, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None,
+                       with_normal=False, with_distortion=False):
+    """render_packed() with the cone-stepped march through a cascade of occupancy grids (include/lab4d_conemarch.h), for a scene box many
+    times as wide as the object: packed.march_cone(cascade, origin, dir, t_range, cone, dt_min, dt_max, cap, k_max) steps every ray at
+    s = clamp(a * cone, dt_min, dt_max) and keeps a candidate iff its bit is set at the cascade level that fits its position and its step;
+    forward() runs on the kept rows (P["aabb"] is the cascade's outermost box; the parked rows lie outside it) and packed.composite renders
+    them with each row's OWN delta = s |dir|.  Returns what render_packed returns: (rgb (R,3), mask (R,1), depth (R,1), total, overflow), then
+    `normal (R,3)` with with_normal=True, then `distortion (R,1)` with with_distortion=True: packed.distortion with mid = t and width = steps
+    per row, in the units of t.  Gradients flow to the table, the Linears and logibeta."""
+    rays = packed.march_cone(cascade, origin, dir, t_range, cone, dt_min, dt_max, cap, k_max=k_max)
+    rgb_s, dens_s = forward(P, cfg, rays.xyz, rays.dirs, spf=max(int(cap), 1), prec=prec, res=res, table_grad_f16=table_grad_f16)
+    fields = {"rgb": rgb_s, "depth": rays.t[:, None]}
+    if with_normal:
+        fields["normal"] = normals(P, cfg, rays.xyz, res=res)
+    rendered, mask = packed.composite(dens_s, rays.deltas, fields, rays)
+    out = (rendered["rgb"], mask, rendered["depth"], rays.total, rays.overflow)
+    if with_normal:
+        out += (rendered["normal"],)
+    return out + (packed.distortion(dens_s, rays.deltas, rays.t, rays.steps, rays)[:, None],) if with_distortion else out
 
 
 def density(P, cfg, xyz, prec=mlp.PREC_F32, res=None):

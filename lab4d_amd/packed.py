@@ -10,7 +10,9 @@ order: a foreground field in front of a background, composited as one list.  `we
 (include/lab4d_presample.h, csrc/presample.hip) are the coarse-to-fine step: the compositing weights of a list without gradients, and the
 inverse-CDF resampling of the list into n_imp rows per ray where those weights are.  `render_weights` and `proposal_loss`
 (include/lab4d_proposal.h, csrc/proposal.hip) train a proposal field for that step: the weights with a backward, and the interval loss
-that makes a proposal list's weights an upper envelope of the fine list's.  Nothing here synchronises
+that makes a proposal list's weights an upper envelope of the fine list's.  `march_cone` (include/lab4d_conemarch.h, csrc/conemarch.hip) is
+`march` with a step that grows with the distance, through a cascade of occupancy grids (occgrid.OccupancyCascade): the same packed layout
+with a step and a level per row, which everything above takes as it is.  Nothing here synchronises
 with the host: every call can be captured in a hipGraph."""
 import collections
 import math
@@ -75,6 +77,60 @@ def march(grid, origin, dir, t_range, dt, cap, k_max=1024):
     _lib.call("packed_march_write", *head, start, cap, out["t"], out["deltas"], out["xyz"], out["dirs"], out["ray_idx"], out["ray_count"], out["total"],
               overflow)
     return PackedRays(ray_start=start, overflow=overflow.view(torch.bool), R=R, cap=cap, **out)
+
+
+class ConeRays(PackedRays):
+    """The packed list of one cone-stepped march: a PackedRays whose rows also carry steps (cap,), the row's own step s_k in the units of t
+    (deltas = steps * |dir|: per row, not per ray), and level (cap,) int32, the cascade level the row was looked up in (-1 in the parked
+    rows, whose steps are 0)."""
+    __slots__ = ("steps", "level")
+
+    def __init__(self, **kw):
+        for k in PackedRays.__slots__ + self.__slots__:
+            setattr(self, k, kw[k])
+
+
+@torch.no_grad()
+def march_cone(cascade, origin, dir, t_range, cone, dt_min, dt_max, cap, k_max=1024):
+    """cascade: occgrid.OccupancyCascade; origin, dir (R,3), t_range (R,2) = [t0, t1] in the units of `dir`; the step grows with the ray
+    parameter, s = clamp(a * cone, dt_min, dt_max) from the ray's entry into the outermost box on, each interval [a, a + s] giving one
+    candidate at its middle; a candidate is kept iff its bit is set at the cascade level that fits its position and its step (rules:
+    include/lab4d_conemarch.h).  cone >= 0 (0: a fixed step dt_min), 0 < dt_min <= dt_max; cap: the STATIC number of packed rows; k_max: at
+    most this many candidates per ray.  -> ConeRays, accepted as it is by composite, prune, distortion, weights / resample, merge and
+    render_weights / proposal_loss.  Two kernels (count, write) around one prefix sum; no read-back."""
+    R, cone, dt_min, dt_max, cap, k_max = origin.shape[0], float(cone), float(dt_min), float(dt_max), int(cap), int(k_max)
+    if not (math.isfinite(cone) and cone >= 0):  # (the scalars first: refused whatever the tensors are)
+        raise RuntimeError("lab4d_amd.packed.march_cone: cone = %r must be finite and >= 0" % cone)
+    if not (math.isfinite(dt_min) and dt_min > 0):
+        raise RuntimeError("lab4d_amd.packed.march_cone: dt_min = %r must be finite and > 0" % dt_min)
+    if not (math.isfinite(dt_max) and dt_max >= dt_min):
+        raise RuntimeError("lab4d_amd.packed.march_cone: dt_max = %r must be finite and >= dt_min = %r" % (dt_max, dt_min))
+    if k_max < 1:
+        raise RuntimeError("lab4d_amd.packed.march_cone: k_max = %d must be >= 1" % k_max)
+    if R * k_max >= 1 << 31:
+        raise RuntimeError("lab4d_amd.packed.march_cone: R * k_max = %d * %d does not fit 31 bits" % (R, k_max))
+    if not 0 <= cap < 1 << 31:
+        raise RuntimeError("lab4d_amd.packed.march_cone: cap = %d outside [0, 2^31)" % cap)
+    _f32("origin", origin, 3)
+    _f32("dir", dir, 3)
+    _f32("t_range", t_range, 2)
+    if dir.shape[0] != R or t_range.shape[0] != R:
+        raise RuntimeError("lab4d_amd.packed.march_cone: origin %s, dir %s and t_range %s disagree on the number of rays"
+                           % (tuple(origin.shape), tuple(dir.shape), tuple(t_range.shape)))
+    dev = origin.device
+    origin, dir, t_range = origin.detach(), dir.detach(), t_range.detach()
+    count = torch.empty(R, dtype=torch.int32, device=dev)
+    head = [origin, dir, t_range, cascade.aabbs, cascade.bits, cascade.K, cascade.G, R, cone, dt_min, dt_max, k_max]
+    _lib.call("packed_march_cone_count", *head, count)
+    start = torch.cumsum(count, 0, dtype=torch.int32) - count  # (the exclusive scan: R * k_max < 2^31, the sums fit)
+    out = {"t": torch.empty(cap, device=dev), "steps": torch.empty(cap, device=dev), "deltas": torch.empty(cap, device=dev),
+           "xyz": torch.empty(cap, 3, device=dev), "dirs": torch.empty(cap, 3, device=dev), "ray_idx": torch.empty(cap, dtype=torch.int32, device=dev),
+           "level": torch.empty(cap, dtype=torch.int32, device=dev), "ray_count": torch.empty(R, dtype=torch.int32, device=dev),
+           "total": torch.empty(1, dtype=torch.int32, device=dev)}
+    overflow = torch.empty(1, dtype=torch.uint8, device=dev)
+    _lib.call("packed_march_cone_write", *head, start, cap, out["t"], out["steps"], out["deltas"], out["xyz"], out["dirs"], out["ray_idx"], out["level"],
+              out["ray_count"], out["total"], overflow)
+    return ConeRays(ray_start=start, overflow=overflow.view(torch.bool), R=R, cap=cap, **out)
 
 
 def _field_list(fields, modes):
