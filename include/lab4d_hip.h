@@ -346,6 +346,13 @@ int lab4d_global_match_backward(const float* feat_px, const float* feat_c, const
  * ------------------------------------------------------------------------------------------ */
 #include "lab4d_conemarch.h"
 
+/* ------------------------------------------------------------------------------------------
+ * 25. Camera-visibility culling of the occupancy grids of 12 and 24: the cells no training camera sees are cleared and stay cleared
+ *     (Instant-NGP's mark_untrained_density_grid, nerfacc's mark_invisible_cells; not in the reference, parity unpinned).
+ *     See lab4d_occvis.h.
+ * ------------------------------------------------------------------------------------------ */
+#include "lab4d_occvis.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC,
           "-Wno-unused-value", "-Wno-pass-failed"] + os.environ.get("LAB4D_HIPCC_EXTRA", "").split()
+# (No -ffast-math and no relaxed fp64 division or square root here, ever: csrc/hd_math.hpp (sqrt_rn) and csrc/occvis_math.hpp (cell_axis_box)
+# take the IEEE double root and quotient as given on the device, and the GPU suite holds the kernels word for word to g++'s.)
 
 
 # the chain-kernel instantiation units only: LLVM's "unclustered high register pressure" rescheduling stage sinks the LDS reads of the shared

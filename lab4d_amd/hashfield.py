@@ -40,7 +40,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from . import hashgrid, hashsdf, hashtrace, mlp, packed
+from . import hashgrid, hashsdf, hashtrace, mlp, occgrid, packed
 from . import render_utils as RU
 from .deformable import volsdf_density
 
@@ -89,12 +89,8 @@ def forward(P, cfg, xyz, dirs, spf, prec=mlp.PREC_F32, res=None, get_density=Tru
     return rgb * inside, ((volsdf_density(sdf, P["logibeta"]) * inside) if get_density else sdf)
 
 
-@torch.no_grad()
-def update_occupancy(P, cfg, grid, prec=mlp.PREC_F32, chunk=1 << 22):
-    """Refreshes an occgrid.OccupancyGrid from the field: the density at the grid's cell centres through forward() (in pieces of `chunk`
-    points; the view direction does not enter the density), then grid.update -- ema = max(ema * decay, density), bit = ema > thresh.
-    Nothing is read back.  Returns the grid."""
-    pts = grid.cell_centers()
+def _density_at(P, cfg, pts, prec, chunk):
+    """forward()'s density at pts (S,3) in pieces of `chunk` points -> (S,); the view direction does not enter the density"""
     dens = torch.empty(pts.shape[0], dtype=torch.float32, device=pts.device)
     res = resolutions(cfg, pts.device)
     for o in range(0, pts.shape[0], chunk):
@@ -102,7 +98,41 @@ def update_occupancy(P, cfg, grid, prec=mlp.PREC_F32, chunk=1 << 22):
         d = torch.zeros_like(x)
         d[:, 2] = 1.0
         dens[o:o + chunk] = forward(P, cfg, x, d, spf=x.shape[0], prec=prec, res=res)[1][:, 0]
-    return grid.update(dens)
+    return dens
+
+
+def _density_where(P, cfg, pts, need, cap, prec, chunk):
+    """_density_at on the rows of pts (S,3) whose `need` (S,) bool is set, 0 on the others, in the manner of forward_compacted: the library's
+    stream compaction, a gather into `cap` rows (STATIC), the rows behind the count parked outside P["aabb"], a scatter into zeros.
+    -> (dens (S,), overflow (1,) bool = more than `cap` rows were needed: the rows behind it got 0).  Nothing is read back."""
+    S = pts.shape[0]
+    if cap is None or int(cap) < 1:
+        raise RuntimeError("hashfield: visible_only=True needs cap, the static number of rows the field is evaluated on (>= 1; a capacity of "
+                           "all %d cells would save nothing), got %s" % (S, cap))
+    cap = int(cap)
+    lo, hi = P["aabb"][0], P["aabb"][1]
+    idx, count = RU.compact(need.to(torch.uint8))
+    live = (torch.arange(cap, device=pts.device, dtype=torch.int32) < count)[:, None]
+    x = torch.where(live, RU.gather_rows_ad(pts, idx, count, cap), (hi + (hi - lo)).to(pts.dtype).expand(cap, 3)).contiguous()
+    dens = _density_at(P, cfg, x, prec, chunk)[:, None] * live.to(torch.float32)
+    return RU.scatter_rows_ad(dens, idx, count, S)[:, 0].contiguous(), count > cap
+
+
+@torch.no_grad()
+def update_occupancy(P, cfg, grid, prec=mlp.PREC_F32, chunk=1 << 22, visible_only=False, cap=None):
+    """Refreshes an occgrid.OccupancyGrid from the field: the density at the grid's cell centres through forward() (in pieces of `chunk`
+    points; the view direction does not enter the density), then grid.update -- ema = max(ema * decay, density), bit = ema > thresh.
+    Nothing is read back.  Returns the grid.
+    visible_only=True (a grid that grid.cull_invisible has culled): the field is evaluated at the centres of the VISIBLE cells only, compacted
+    into `cap` rows (a STATIC capacity, required: e.g. int(grid.n_visible) read once after the cull); every other cell gets density 0, which the cull makes of it anyway:
+    bits, n_occupied and the ema of the visible cells equal those of the full refresh.  Returns (grid, overflow (1,) bool)."""
+    pts = grid.cell_centers()
+    if not visible_only:
+        return grid.update(_density_at(P, cfg, pts, prec, chunk))
+    if grid.visible is None:
+        raise RuntimeError("hashfield.update_occupancy: visible_only=True needs a grid culled by cull_invisible")
+    dens, overflow = _density_where(P, cfg, pts, occgrid.unpack_bits(grid.visible, grid.G), cap, prec, chunk)
+    return grid.update(dens), overflow
 
 
 def forward_compacted(P, cfg, xyz, dirs, cap, prec=mlp.PREC_F32, res=None, get_density=True, table_grad_f16=False, occ=None):
@@ -207,25 +237,27 @@ def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32
 
 
 @torch.no_grad()
-def update_occupancy_cascade(P, cfg, cascade, prec=mlp.PREC_F32, chunk=1 << 22):
+def update_occupancy_cascade(P, cfg, cascade, prec=mlp.PREC_F32, chunk=1 << 22, visible_only=False, cap=None):
     """Refreshes an occgrid.OccupancyCascade from the field: the density at every level's cell centres through forward() (in pieces of
     `chunk` points), then cascade.update -- the propagation from fine to coarse, then ema = max(ema * decay, density), bit = ema > thresh
     per level.  The field lives on the OUTERMOST box, as in the paper: P["aabb"] must equal cascade.aabbs[K - 1], which is checked first
-    (the one read-back of this call) and raises otherwise.  Returns the cascade."""
+    (the one read-back of this call) and raises otherwise.  Returns the cascade.
+    visible_only=True (a cascade that cascade.cull_invisible has culled): the field is evaluated on cascade.refresh_set() only -- the visible
+    cells and the cells below a visible cell of a coarser level, whose density the propagation carries into that visible cell -- compacted
+    into `cap` rows (a STATIC capacity, required: e.g. int(cascade.refresh_set().sum()) read once after the cull); every other cell gets density 0.  bits, n_occupied and the ema
+    of the visible cells equal those of the full refresh.  Returns (cascade, overflow (1,) bool)."""
     outer = cascade.aabbs[cascade.K - 1]
     box = P["aabb"]
     if box.numel() != 6 or not torch.equal(box.detach().reshape(6).to(device=outer.device, dtype=torch.float32), outer):
         raise RuntimeError("hashfield.update_occupancy_cascade: P[\"aabb\"] must be the cascade's outermost box aabbs[K - 1] = %s, got %s"
                            % (outer.tolist(), box.reshape(-1).tolist()))
     pts = cascade.cell_centers().reshape(-1, 3)
-    dens = torch.empty(pts.shape[0], dtype=torch.float32, device=pts.device)
-    res = resolutions(cfg, pts.device)
-    for o in range(0, pts.shape[0], chunk):
-        x = pts[o:o + chunk]
-        d = torch.zeros_like(x)
-        d[:, 2] = 1.0
-        dens[o:o + chunk] = forward(P, cfg, x, d, spf=x.shape[0], prec=prec, res=res)[1][:, 0]
-    return cascade.update(dens.reshape(cascade.K, -1))
+    if not visible_only:
+        return cascade.update(_density_at(P, cfg, pts, prec, chunk).reshape(cascade.K, -1))
+    if cascade.visible is None:
+        raise RuntimeError("hashfield.update_occupancy_cascade: visible_only=True needs a cascade culled by cull_invisible")
+    dens, overflow = _density_where(P, cfg, pts, cascade.refresh_set().reshape(-1), cap, prec, chunk)
+    return cascade.update(dens.reshape(cascade.K, -1)), overflow
 
 
 def render_packed_cone(P, cfg, cascade, origin, dir, t_range, cone, dt_min, dt_max, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None,

@@ -3,7 +3,9 @@ refreshed from the field's own density (hashfield.update_occupancy), consulted p
 hashfield.forward_compacted) and per ray (`ray_span` / `ray_depths`: march only between the first and the last occupied cell).  The
 reference has no counterpart (nnutils/nerf.py:98 is a TODO); the rules are written down in the header and in csrc/occgrid_math.hpp.
 OccupancyCascade is K such grids around one centre, each twice the extent of the one before, for a scene box many times as wide as the
-object (include/lab4d_conemarch.h, csrc/conemarch.hip): what packed.march_cone marches through.  Nothing here synchronises with the host: every call can be captured in a hipGraph."""
+object (include/lab4d_conemarch.h, csrc/conemarch.hip): what packed.march_cone marches through.  `camera_planes` and `cull_invisible` clear the cells that no training camera sees
+(include/lab4d_occvis.h, csrc/occvis.hip), for good: a later update applies the cull again.  Nothing here synchronises with the host: every
+call can be captured in a hipGraph."""
 import torch
 
 from . import _lib
@@ -15,9 +17,74 @@ def _f32(name, t, *shape_tail):
         raise RuntimeError("lab4d_amd.occgrid: %s must be float32 (..., %s), got %s %s" % (name, ", ".join(map(str, shape_tail)), t.dtype, tuple(t.shape)))
 
 
+def camera_planes(Kmat, field2cam, wh, near, far=None, pad=0.0):
+    """The six half-spaces of M camera frusta in the field's frame (VIEWS and CAMERA of include/lab4d_occvis.h): Kmat (M, 4) = {fx, fy, cx, cy},
+    field2cam (M, 4, 4) or (M, 3, 4) = [R | t] with x_cam = R x_field + t, wh = (W, H) pixels, near and far depths (far None: no far plane,
+    encoded as (0, 0, 0, 1)), pad in pixels widens the image on every side.  -> planes (M, 6, 4) fp32 = {nx, ny, nz, d}, unit normals, a point
+    is inside iff n.x + d >= 0; order left, right, top, bottom, near, far.  Torch ops in float64 on the inputs' device (no kernel: a host tensor
+    gives host planes), rounded to fp32 once."""
+    M = Kmat.shape[0]
+    if Kmat.ndim != 2 or Kmat.shape[1] != 4 or field2cam.ndim != 3 or field2cam.shape[0] != M or tuple(field2cam.shape[1:]) not in ((4, 4), (3, 4)):
+        raise RuntimeError("lab4d_amd.occgrid.camera_planes: Kmat must be (M, 4) and field2cam (M, 4, 4) or (M, 3, 4), got %s and %s"
+                           % (tuple(Kmat.shape), tuple(field2cam.shape)))
+    W, H = float(wh[0]), float(wh[1])
+    near, pad = float(near), float(pad)
+    Kd, E = Kmat.detach().to(torch.float64), field2cam.detach().to(torch.float64)
+    fx, fy, cx, cy = Kd.unbind(1)
+    zero, one = torch.zeros_like(fx), torch.ones_like(fx)
+    rows = [(fx, zero, cx + pad, zero), (-fx, zero, W + pad - cx, zero), (zero, fy, cy + pad, zero), (zero, -fy, H + pad - cy, zero),
+            (zero, zero, one, zero - near)]
+    if far is not None:
+        rows.append((zero, zero, -one, zero + float(far)))
+    cam = torch.stack([torch.stack(r, -1) for r in rows], 1)  # (M, 5 | 6, 4) in the camera frame
+    x, y, z = cam[..., 0], cam[..., 1], cam[..., 2]
+    cam = cam / torch.sqrt(x * x + y * y + z * z)[..., None]
+    x, y, z, d_c = cam.unbind(-1)
+    R, t = E[:, :3, :3], E[:, :3, 3]
+    # n_w = R^T n_c, d_w = n_c . t + d_c, every sum from left to right (the float64 statement of the tests adds in the same order)
+    n_w = [R[:, None, 0, i] * x + R[:, None, 1, i] * y + R[:, None, 2, i] * z for i in range(3)]
+    d_w = x * t[:, None, 0] + y * t[:, None, 1] + z * t[:, None, 2] + d_c
+    planes = torch.stack(n_w + [d_w], -1)
+    if far is None:
+        open_far = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64, device=planes.device).expand(M, 1, 4)
+        planes = torch.cat([planes, open_far], 1)
+    return planes.to(torch.float32).contiguous()
+
+
+def _mark_visible(planes, aabbs, K, G, min_views):
+    """lab4d_occvis_mark on K boxes: (vis_bits (K, words) int32, n_visible (K,) int32)"""
+    _lib.require_device(planes)
+    if planes.dtype != torch.float32 or planes.ndim != 3 or tuple(planes.shape[1:]) != (6, 4) or planes.shape[0] < 1:
+        raise RuntimeError("lab4d_amd.occgrid.cull_invisible: planes must be float32 (M >= 1, 6, 4), got %s %s" % (planes.dtype, tuple(planes.shape)))
+    M, min_views = planes.shape[0], int(min_views)
+    if not 1 <= min_views <= M:
+        raise RuntimeError("lab4d_amd.occgrid.cull_invisible: min_views = %d outside [1, M = %d]" % (min_views, M))
+    vis = torch.empty(K, (G ** 3 + 31) // 32, dtype=torch.int32, device=planes.device)
+    n_vis = torch.empty(K, dtype=torch.int32, device=planes.device)
+    _lib.call("occvis_mark", planes.detach(), M, aabbs, K, G, min_views, vis, n_vis)
+    return vis, n_vis
+
+
+def unpack_bits(words, G):
+    """(..., ceil(G^3 / 32)) int32 words in the GRID layout -> (..., G^3) bool.  Torch ops on the device."""
+    shifts = torch.arange(32, device=words.device, dtype=torch.int32)
+    return ((words[..., None] >> shifts) & 1).bool().reshape(*words.shape[:-1], -1)[..., :G ** 3]
+
+
+def pack_bits(flags):
+    """(..., n) bool -> (..., ceil(n / 32)) int32 words in the GRID layout (the padding bits zero).  Torch ops on the device."""
+    n = flags.shape[-1]
+    f = torch.nn.functional.pad(flags.to(torch.int64), (0, -n % 32)).reshape(*flags.shape[:-1], -1, 32)
+    w = (f << torch.arange(32, device=flags.device, dtype=torch.int64)).sum(-1)
+    return torch.where(w >= 1 << 31, w - (1 << 32), w).to(torch.int32)
+
+
 class OccupancyGrid:
     """bits (ceil(G^3/32),) int32 words (bit idx & 31 of word idx >> 5, idx = (i*G + j)*G + k, x slowest), ema (G^3,) fp32, n_occupied (1,)
-    device int32.  A new grid knows nothing: every bit is set, ema = +inf, and its mask is the box test alone."""
+    device int32.  A new grid knows nothing: every bit is set, ema = +inf, and its mask is the box test alone.  visible (words,) int32 and
+    n_visible (1,) int32 are None until `cull_invisible` sets them."""
+    visible = None
+    n_visible = None
 
     def __init__(self, aabb, G=128, decay=0.95, thresh=0.01):
         G = int(G)
@@ -46,6 +113,19 @@ class OccupancyGrid:
             raise RuntimeError("lab4d_amd.occgrid.update needs a (G, G, G) or (G^3,) float32 density with G = %d, got %s %s"
                                % (self.G, density.dtype, tuple(density.shape)))
         _lib.call("occgrid_update", density, self.ema, self.bits, self.n_occupied, self.G, self.decay, self.thresh)
+        if self.visible is not None:  # a culled cell stays culled: no refresh revives it
+            _lib.call("occvis_apply", self.visible, self.ema, self.bits, self.n_occupied, 1, self.G)
+        return self
+
+    @torch.no_grad()
+    def cull_invisible(self, planes, min_views=1):
+        """Clears the cells that fewer than `min_views` of the views `planes` (M, 6, 4) (camera_planes) see -- the rule of
+        include/lab4d_occvis.h: a cell is kept unless its box lies wholly outside one of a view's six half-spaces, so every point a view
+        sees lies in a kept cell.  Stores the mark as `visible` (words, the layout of `bits`) and `n_visible` (1,), then bits &= visible,
+        ema = 0 on the invisible cells ("known empty") and n_occupied is recounted.  `update` applies the mark again from then on."""
+        vis, n_vis = _mark_visible(planes, self.aabb.reshape(1, 6), 1, self.G, min_views)
+        self.visible, self.n_visible = vis[0], n_vis
+        _lib.call("occvis_apply", self.visible, self.ema, self.bits, self.n_occupied, 1, self.G)
         return self
 
     @torch.no_grad()
@@ -121,7 +201,10 @@ class OccupancyCascade:
     2^c of the base box `aabb` (2, 3) -- computed in float64, rounded once to fp32 -- with the same G cells per axis, so the cells double with
     every level.  aabbs (K, 6) = {lo xyz, hi xyz} per level, bits (K, ceil(G^3 / 32)) int32 words in OccupancyGrid's layout, ema (K, G^3),
     n_occupied (K,) int32.  A new cascade knows nothing: every bit is set and ema = +inf.  1 <= K <= 8; G must be even when K > 1.
-    `packed.march_cone` marches through it; `level_grid(c)` is level c as a plain OccupancyGrid on the same storage."""
+    `packed.march_cone` marches through it; `level_grid(c)` is level c as a plain OccupancyGrid on the same storage.  visible (K, words) int32
+    and n_visible (K,) int32 are None until `cull_invisible` sets them."""
+    visible = None
+    n_visible = None
 
     def __init__(self, aabb, K=4, G=128, decay=0.95, thresh=0.01):
         K, G = int(K), int(G)
@@ -158,6 +241,8 @@ class OccupancyCascade:
         grid = OccupancyGrid.__new__(OccupancyGrid)
         grid.G, grid.decay, grid.thresh = self.G, self.decay, self.thresh
         grid.aabb, grid.bits, grid.ema, grid.n_occupied = self.aabbs[c].view(2, 3), self.bits[c], self.ema[c], self.n_occupied[c:c + 1]
+        if self.visible is not None:
+            grid.visible, grid.n_visible = self.visible[c], self.n_visible[c:c + 1]
         return grid
 
     def cell_centers(self):
@@ -195,8 +280,42 @@ class OccupancyCascade:
                                % (self.K, self.G, density.dtype, tuple(density.shape)))
         d = self.propagate(density.reshape(self.K, -1))
         for c in range(self.K):
-            self.level_grid(c).update(d[c])
+            _lib.call("occgrid_update", d[c], self.ema[c], self.bits[c], self.n_occupied[c:c + 1], self.G, self.decay, self.thresh)
+        if self.visible is not None:  # a culled cell stays culled: one apply for all K levels behind the update kernels
+            _lib.call("occvis_apply", self.visible, self.ema, self.bits, self.n_occupied, self.K, self.G)
         return self
+
+    @torch.no_grad()
+    def cull_invisible(self, planes, min_views=1):
+        """OccupancyGrid.cull_invisible on every level (one lab4d_occvis_mark launch for all K boxes, one lab4d_occvis_apply).  Between
+        the two the visible set of level c is raised to contain the 2 x 2 x 2 pool of level c - 1's (`propagate` on the unpacked marks),
+        so that the parent property `update` documents survives the cull: a coarse bit is set wherever one of its eight children is, also
+        where G is no multiple of 4.  (The box test alone nearly gives that -- a parent's box contains its children's -- but not to the
+        last rounding.)  `visible` (K, words) and `n_visible` (K,) hold the raised marks; level_grid(c) shares them."""
+        vis, n_vis = _mark_visible(planes, self.aabbs, self.K, self.G, min_views)
+        if self.K > 1:
+            flags = self.propagate(unpack_bits(vis, self.G).to(torch.float32)) > 0
+            vis, n_vis = pack_bits(flags).contiguous(), flags.sum(1).to(torch.int32)
+        self.visible, self.n_visible = vis, n_vis
+        _lib.call("occvis_apply", self.visible, self.ema, self.bits, self.n_occupied, self.K, self.G)
+        return self
+
+    @torch.no_grad()
+    def refresh_set(self):
+        """(K, G^3) bool: the cells whose density can reach the ema of a visible cell through `propagate` -- the visible cells and every
+        cell below a visible cell of a coarser level (the propagation runs from fine to coarse, so an invisible child raises a visible
+        parent).  What hashfield.update_occupancy_cascade(visible_only=True) evaluates; None visible: every cell."""
+        K, G = self.K, self.G
+        if self.visible is None:
+            return torch.ones(K, G ** 3, dtype=torch.bool, device=self.bits.device)
+        need = unpack_bits(self.visible, G).reshape(K, G, G, G).clone()
+        pad = 1 if G % 4 else 0
+        o, n = (G - 2 * pad) // 4, (G + 2 * pad) // 2
+        for c in range(K - 2, -1, -1):  # the block of level c + 1 that covers level c, each cell over its 2 x 2 x 2 children (see propagate)
+            block = need[c + 1, o:o + n, o:o + n, o:o + n]
+            below = block.repeat_interleave(2, 0).repeat_interleave(2, 1).repeat_interleave(2, 2)
+            need[c] |= below[pad:pad + G, pad:pad + G, pad:pad + G]
+        return need.reshape(K, G ** 3)
 
     @torch.no_grad()
     def mask(self, xyz, delta=None):
