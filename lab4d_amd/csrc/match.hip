@@ -2,9 +2,10 @@
 //   score = (feat_px @ feat_c^T) * exp(logsigma);  prob = softmax(score, 1);  xyz_matched = prob @ xyz_c
 // as one kernel forward and two backward (the reference's matmul / mul / softmax / matmul and their adjoints stream the (R, K) score
 // matrix eight times: 4 GB per 131,072 rays; here it never exists).  Contract: include/lab4d_hip.h (section 3d).
-// Forward / backward-by-ray: one thread per ray, the candidates (K x 16 features, K x 3 points) in LDS, read as broadcasts.
-// Backward-by-candidate: a resident grid; each thread owns K/256 candidates in registers and walks its block's rays (staged through LDS);
-// per-block partials go to a workspace and are summed by a last small kernel (no atomics: 19 K floats per block).
+// Forward: one thread per ray, the candidates (K x 16 features, K x 3 points) in LDS, read as broadcasts.
+// Backward, by candidate (the pixel features are data: there is no gradient by ray): a resident grid; each thread owns ceil(K/256)
+// candidates in registers and walks its block's rays (staged through LDS); per-block partials go to a workspace and are summed by a last
+// small kernel (no atomics: 20 K floats per block).
 #include "common.hpp"
 
 namespace lab4d {
@@ -12,13 +13,18 @@ namespace lab4d {
 constexpr int MC = 16;       // feature channels
 constexpr int MKMAX = 1024;  // candidates
 
+// f . row as ONE rounded product and fifteen explicit fused multiply-adds.  Written as s += f[c] * row[c] the contraction is the compiler's
+// choice per call site, and it differs between the two passes of k_match_fwd (the first six terms fused in one, the first eight in the
+// other): on a ray in a few hundred the score of the row maximum then differs between the passes in its last bit, its exponential is
+// 1 - 2^-24 instead of 1, the sum of exponentials falls below 1, and with a single candidate out is not the candidate's point (nor
+// the gradients of feat_c and logsigma zero).  Both passes must see the same score: tests/test_gpu_match.py, K = 1 at R >= 257.
 __device__ __forceinline__ float dot16(const float (&f)[MC], const float4* row) {
   const float4 a = row[0], b = row[1], c = row[2], d = row[3];
   float s = f[0] * a.x;
-  s += f[1] * a.y; s += f[2] * a.z; s += f[3] * a.w;
-  s += f[4] * b.x; s += f[5] * b.y; s += f[6] * b.z; s += f[7] * b.w;
-  s += f[8] * c.x; s += f[9] * c.y; s += f[10] * c.z; s += f[11] * c.w;
-  s += f[12] * d.x; s += f[13] * d.y; s += f[14] * d.z; s += f[15] * d.w;
+  s = __builtin_fmaf(f[1], a.y, s); s = __builtin_fmaf(f[2], a.z, s); s = __builtin_fmaf(f[3], a.w, s);
+  s = __builtin_fmaf(f[4], b.x, s); s = __builtin_fmaf(f[5], b.y, s); s = __builtin_fmaf(f[6], b.z, s); s = __builtin_fmaf(f[7], b.w, s);
+  s = __builtin_fmaf(f[8], c.x, s); s = __builtin_fmaf(f[9], c.y, s); s = __builtin_fmaf(f[10], c.z, s); s = __builtin_fmaf(f[11], c.w, s);
+  s = __builtin_fmaf(f[12], d.x, s); s = __builtin_fmaf(f[13], d.y, s); s = __builtin_fmaf(f[14], d.z, s); s = __builtin_fmaf(f[15], d.w, s);
   return s;
 }
 
@@ -84,10 +90,13 @@ __global__ void __launch_bounds__(256) k_match_bwd_cand(const float* __restrict_
   __shared__ float red[256];
   const float scale = expf(*logsigma);
   float cf[NCT][MC], cx[NCT][3], gf[NCT][MC], gx[NCT][3];
-  float gls = 0.f;
+  // the g_logsigma share per owned candidate, not per thread: a padded candidate (i >= K: features 0, score 0) has the weight
+  // exp(0 - max) / l, which is infinite where every score of a row is below -88.7, and inf * 0 must not reach the sum
+  float gls[NCT];
 #pragma unroll
   for (int j = 0; j < NCT; ++j) {
     const int i = threadIdx.x + 256 * j;
+    gls[j] = 0.f;
 #pragma unroll
     for (int c = 0; c < MC; ++c) { cf[j][c] = i < K ? fc[(size_t)i * MC + c] : 0.f; gf[j][c] = 0.f; }
 #pragma unroll
@@ -126,12 +135,16 @@ __global__ void __launch_bounds__(256) k_match_bwd_cand(const float* __restrict_
 #pragma unroll
         for (int c = 0; c < MC; ++c) gf[j][c] += ds * f[c];
         gx[j][0] += p * g0; gx[j][1] += p * g1; gx[j][2] += p * g2;
-        gls += ds * s;
+        gls[j] += ds * s;
       }
     }
   }
   // block partials: (K, 20) = [g_fc (16, scaled) | g_xc (3) | g_logsigma share]
-  red[threadIdx.x] = gls;
+  float gsum = 0.f;
+#pragma unroll
+  for (int j = 0; j < NCT; ++j)
+    if ((int)threadIdx.x + 256 * j < K) gsum += gls[j];
+  red[threadIdx.x] = gsum;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
     if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
