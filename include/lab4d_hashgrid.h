@@ -39,4 +39,26 @@ int lab4d_hashgrid_backward_f16(const float* x, const float* table, const int32_
                                 int first_f16_level, float* g_table, uint32_t* g16, const uint32_t* absmax_bits, float* g_x, void* stream);
 int lab4d_hashgrid_flush_f16(uint32_t* g16, const uint32_t* absmax_bits, int L, int log2_T, int first_f16_level, float* g_table, void* stream);
 
+/* Footprint-weighted levels for anti-aliased cone marching (Barron et al. 2023, "Zip-NeRF", section 2.2; lab4d_amd/csrc/hashgrid_math.hpp
+ * level_weight).  radius (S): the isotropic Gaussian radius of every sample in the unit cube.  Level l of sample s is multiplied by
+ *     w = 1                                         if !(radius[s] > 0)      (0, negative, NaN: a point sample, the unweighted encoding)
+ *     w = erf(1 / (sqrt(8) * radius[s] * res[l]))   otherwise                (+inf: 0)
+ *     w = 0                                         where w < w_min          (per sample; w_min = 0 cuts nothing; 0 <= w_min <= 1, finite)
+ * out[s][l*F + f] = w * (what lab4d_hashgrid_forward writes); the adjoint scales the level's g_out entries by w before the unweighted adjoint runs
+ * on them (the table gradient and g_x both), and radius itself gets no gradient.  Where w = 0 the forward reads nothing of the level's table,
+ * and a level whose w * g_out entries are zero for all 64 samples of a wave is skipped in the backward as above: the fine levels of far samples
+ * cost no gathers and no atomics.
+ *   lab4d_hashgrid_forward_aa: inside_only = 0 is lab4d_hashgrid_forward's kernel, != 0 lab4d_hashgrid_forward_inside's two (the level-major one
+ *     from S = 65536 on, where a thread with w = 0 writes its zeros without touching the level's slab).
+ *   lab4d_hashgrid_backward_aa / lab4d_hashgrid_backward_f16_aa: lab4d_hashgrid_backward / lab4d_hashgrid_backward_f16 with the weighting.
+ *     absmax_bits is still lab4d_hashgrid_absmax of the UNWEIGHTED g_out: w <= 1, so no weighted entry exceeds it and the headroom of the
+ *     fp16 scale (the largest single contribution at 2^8) holds unchanged; lab4d_hashgrid_flush_f16 is shared. */
+int lab4d_hashgrid_forward_aa(const float* x, const float* radius, const float* table, const int32_t* res, int S, int L, int log2_T, int F,
+                              float w_min, int inside_only, float* out, void* stream);
+int lab4d_hashgrid_backward_aa(const float* x, const float* radius, const float* table, const int32_t* res, const float* g_out, int S, int L,
+                               int log2_T, int F, float w_min, float* g_table, float* g_x, void* stream);
+int lab4d_hashgrid_backward_f16_aa(const float* x, const float* radius, const float* table, const int32_t* res, const float* g_out, int S, int L,
+                                   int log2_T, int first_f16_level, float w_min, float* g_table, uint32_t* g16, const uint32_t* absmax_bits,
+                                   float* g_x, void* stream);
+
 #endif /* LAB4D_HASHGRID_H */

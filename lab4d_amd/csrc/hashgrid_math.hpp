@@ -55,6 +55,18 @@ LAB4D_HD void encode_level(const float* x, const float* tab, int res, int log2_T
     }
 }
 
+// Footprint weight of a level (Barron et al., "Zip-NeRF", 2023, section 2.2): a sample that stands for an isotropic Gaussian of radius `radius`
+// (in the unit cube) reads level `res` down-weighted by how much of a cell the Gaussian covers,  w = erf(1 / (sqrt(8) * radius * res)).
+//   !(radius > 0) -- zero, negative, NaN: exactly 1 (a point sample reads the unweighted encoding); radius = +inf: z = 0 and w = 0;
+//   w < w_min: exactly 0 (a PER-SAMPLE cut, never a property of the wave; w_min = 0 cuts nothing).
+// The weighted encoding is  out[l*F + f] = w * encode_level(...)[f];  its adjoint is encode_level_bwd with g[f] * w in place of g[f].
+LAB4D_HD float level_weight(float radius, int res, float w_min) {
+    if (!(radius > 0.f)) return 1.f;
+    const float z = 1.f / (2.8284271f * radius * (float)res);
+    const float w = erff(z);
+    return (w < w_min) ? 0.f : w;
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 // g_tab[v + f] += val[f] for every lane of the wave, with the lanes of a RUN of equal consecutive vertices combined first (segmented
 // inclusive scan over the 64 lanes, one atomic per run and feature from its last lane).  Lanes are consecutive samples of a ray, and a

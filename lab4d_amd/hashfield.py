@@ -24,7 +24,9 @@ weights of that list without gradients, and the differentiable field on n_imp ro
 (include/lab4d_presample.h).  render_packed_proposal() takes those weights from a second, cheaper hash field instead and returns the interval loss
 that trains it (include/lab4d_proposal.h).  render_packed_cone() is render_packed() for a scene box many times as wide as the object: the step
 grows with the distance and every sample is looked up in a cascade of occupancy grids (occgrid.OccupancyCascade, refreshed with
-update_occupancy_cascade(); include/lab4d_conemarch.h).  All of it is opt-in.
+update_occupancy_cascade(); include/lab4d_conemarch.h).  render_packed(footprint=...) and render_packed_cone(footprint=...) anti-alias the far
+field: every row is a Gaussian of radius sample_radius() and reads the encoding's levels footprint-weighted (forward(radius=...);
+include/lab4d_hashgrid.h).  All of it is opt-in.
 
 The SDF as an SDF: sdf_gradient() returns the sdf with its gradient in the point from one fused kernel (hashsdf.py, include/lab4d_hashsdf.h),
 differentiable in the table and the geometry net; eikonal_loss() and normals() build on it (the counterparts of nnutils/nerf.py:416-493), and
@@ -67,9 +69,18 @@ def resolutions(cfg, device):
     return torch.tensor(hashgrid.level_resolutions(cfg["L"], cfg["n_min"], cfg["n_max"]), dtype=torch.int32, device=device)
 
 
-def forward(P, cfg, xyz, dirs, spf, prec=mlp.PREC_F32, res=None, get_density=True, table_grad_f16=False):
+def _radius01(P, radius):
+    """a metric radius in the units of xyz -> the unit cube's: over the SMALLEST edge of P["aabb"], the axis with the smallest cells, so that
+    the footprint weights are alias-free on every axis"""
+    return (radius.float() / (P["aabb"][1] - P["aabb"][0]).detach().min()).contiguous()
+
+
+def forward(P, cfg, xyz, dirs, spf, prec=mlp.PREC_F32, res=None, get_density=True, table_grad_f16=False, radius=None, w_min=0.0):
     """xyz, dirs (S,3) -> rgb (S,3), density or sdf (S,1).  spf = samples per frame (the chain kernels' frame stride; the hash nets have
-    no per-frame conditioning, any positive value does)."""
+    no per-frame conditioning, any positive value does).
+    radius (S,), optional: every sample's isotropic Gaussian radius in the units of xyz (sample_radius() for a marched list); the encoding's
+    levels are footprint-weighted (hashgrid.hash_encode(radius=..., w_min=...)): a sample wider than a level's cells reads less of that level,
+    and nothing of it below the weight w_min.  0 in a row is a point sample.  No gradient reaches radius.  None: the unweighted encoding."""
     if cfg["L"] * cfg["F"] != 32:
         raise NotImplementedError("hash field: the geometry net is instantiated for L*F = 32 hash features")
     lo, hi = P["aabb"][0], P["aabb"][1]
@@ -77,7 +88,12 @@ def forward(P, cfg, xyz, dirs, spf, prec=mlp.PREC_F32, res=None, get_density=Tru
     if res is None:
         res = resolutions(cfg, xyz.device)
     f16_from = hashgrid.first_hashed_level(hashgrid.level_resolutions(cfg["L"], cfg["n_min"], cfg["n_max"]), cfg["log2_T"]) if table_grad_f16 else None
-    enc = hashgrid.hash_encode(x01, P["hash.table"], res, cfg["log2_T"], inside_only=True, f16_from=f16_from)  # (S, 32); zero rows outside the box (masked below)
+    if radius is not None:
+        if radius.requires_grad:
+            raise RuntimeError("hashfield.forward: radius must not require grad: the footprint weights are not differentiated (pass radius.detach())")
+        radius = _radius01(P, radius)
+    enc = hashgrid.hash_encode(x01, P["hash.table"], res, cfg["log2_T"], inside_only=True, f16_from=f16_from, radius=radius,
+                               w_min=w_min)  # (S, 32); zero rows outside the box (masked below)
     geo = mlp.run_chain(mlp.NET_HASH_GEO, prec, P, enc, spf)                       # (S, 16)
     sdf = geo[:, :1]
     rgb = torch.sigmoid(mlp.run_chain(mlp.NET_HASH_COLOR, prec, P, torch.cat([geo, dirs], -1), spf))
@@ -135,7 +151,7 @@ def update_occupancy(P, cfg, grid, prec=mlp.PREC_F32, chunk=1 << 22, visible_onl
     return grid.update(dens), overflow
 
 
-def forward_compacted(P, cfg, xyz, dirs, cap, prec=mlp.PREC_F32, res=None, get_density=True, table_grad_f16=False, occ=None):
+def forward_compacted(P, cfg, xyz, dirs, cap, prec=mlp.PREC_F32, res=None, get_density=True, table_grad_f16=False, occ=None, radius=None, w_min=0.0):
     """forward() with the field evaluated on the samples INSIDE the box only (round 6; VERDICT r05 "next" 6): the box mask, the library's stream
     compaction (device-side count, no host round trip: csrc/compact.hip, what the eval path's get_valid_idx uses), a gather of the points / view
     directions into a buffer of `cap` rows, encoding + both nets + the table gradient on that buffer, a scatter of colour / density into zeros.
@@ -146,8 +162,11 @@ def forward_compacted(P, cfg, xyz, dirs, cap, prec=mlp.PREC_F32, res=None, get_d
     callers check it where they synchronise anyway.  Returns (rgb (S,3), density | sdf (S,1), count (1) int32, overflow (1) bool).
     occ: an occgrid.OccupancyGrid over P["aabb"] (optional): the compaction mask becomes occ.mask(xyz) -- inside the box AND in a cell whose bit
     is set -- so samples in empty cells get zero colour and density and cost nothing behind the mask, like the samples outside the box.  A grid that
-    has not been updated yet has every bit set and changes nothing.  None: the box test alone, as before."""
+    has not been updated yet has every bit set and changes nothing.  None: the box test alone, as before.
+    radius (S,), w_min: forward()'s; the radius is gathered with the points, the parked rows get radius 0."""
     S = xyz.shape[0]
+    if radius is not None and radius.requires_grad:
+        raise RuntimeError("hashfield.forward_compacted: radius must not require grad: the footprint weights are not differentiated (pass radius.detach())")
     lo, hi = P["aabb"][0], P["aabb"][1]
     with torch.no_grad():
         if occ is None:
@@ -161,7 +180,11 @@ def forward_compacted(P, cfg, xyz, dirs, cap, prec=mlp.PREC_F32, res=None, get_d
     xyz_c = RU.gather_rows_ad(xyz, idx, count, cap)
     xyz_c = torch.where(live, xyz_c, (hi + (hi - lo)).expand_as(xyz_c))  # rows behind the count: a point outside the box
     dirs_c = RU.gather_rows_ad(dirs, idx, count, cap)
-    rgb_c, d_c = forward(P, cfg, xyz_c, dirs_c, spf=cap, prec=prec, res=res, get_density=get_density, table_grad_f16=table_grad_f16)
+    radius_c = None
+    if radius is not None:  # (gathered like the points; the rows behind the count are point samples)
+        radius_c = torch.where(live, RU.gather_rows_ad(radius.float().reshape(S, 1), idx, count, cap), torch.zeros((), device=xyz.device))[:, 0].contiguous()
+    rgb_c, d_c = forward(P, cfg, xyz_c, dirs_c, spf=cap, prec=prec, res=res, get_density=get_density, table_grad_f16=table_grad_f16, radius=radius_c,
+                         w_min=w_min)
     if not get_density:
         d_c = d_c * live.to(d_c.dtype)  # (forward() masks density and colour, not the raw sdf)
     return RU.scatter_rows_ad(rgb_c, idx, count, S), RU.scatter_rows_ad(d_c, idx, count, S), count, overflow
@@ -211,8 +234,29 @@ def _packed_distortion(dens_s, rays, dt):
     return packed.distortion(dens_s, rays.deltas, rays.t * rays.deltas / dt, rays.deltas, rays)[:, None]
 
 
+def sample_radius(rays, dir, footprint):
+    """The isotropic Gaussian radius (cap,) of every row of a marched list (packed.march / packed.march_cone), in the units of xyz: the pixel
+    cone's radius at the sample, rays.t * |dir[ray_idx]| * footprint, where `footprint` is the cone's Gaussian radius per unit of metric
+    distance (for a pinhole camera about the pixel's angular width over sqrt(12)).  0 in the parked rows (ray_idx == -1).  No gradients."""
+    with torch.no_grad():
+        live = rays.ray_idx >= 0
+        if dir.shape[0] == 0:  # (no rays: every row is parked)
+            return torch.zeros_like(rays.t)
+        length = dir.detach().norm(2, -1)[rays.ray_idx.clamp_min(0).long()]
+        return torch.where(live, rays.t * length * float(footprint), torch.zeros_like(rays.t)).contiguous()
+
+
+def _footprint_radius(rays, dir, footprint, with_normal):
+    if footprint is None:
+        return None
+    if with_normal:
+        raise NotImplementedError("hashfield: footprint together with with_normal=True: the fused SDF-gradient kernel (csrc/hashsdf.hip) reads the "
+                                  "unweighted encoding")
+    return sample_radius(rays, dir, footprint)
+
+
 def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None, with_normal=False,
-                  with_distortion=False):
+                  with_distortion=False, footprint=None, w_min=1.0 / 256):
     """Renders rays through the hash field with packed marching (include/lab4d_packed.h): packed.march(grid, origin, dir, t_range, dt, cap, k_max)
     keeps the candidates t0 + (k + 0.5) dt of every ray whose cell's bit is set -- what forward_compacted(occ=grid) keeps of the same lattice --
     as one packed list of at most `cap` rows (STATIC: the call is capturable), forward() runs on those rows (the parked rows behind the count lie
@@ -223,9 +267,12 @@ def render_packed(P, cfg, grid, origin, dir, t_range, dt, cap, prec=mlp.PREC_F32
     with_normal=True: normals() of the kept rows is composited like the colour and `normal (R,3)` is appended to the returned tuple (the
     weighted mean of unit normals: not renormalised; gradients reach it through the weights only).  The other five are unchanged.
     with_distortion=True: `distortion (R,1)`, packed.distortion of the kept rows in metric units (width = dt |dir|, mid = t |dir|), is appended
-    LAST, behind `normal` when both are set; gradients reach the table, the geometry Linears and logibeta through the density."""
+    LAST, behind `normal` when both are set; gradients reach the table, the geometry Linears and logibeta through the density.
+    footprint: the pixel cone's Gaussian radius per unit of metric distance (optional): forward() gets radius = sample_radius(rays, dir, footprint)
+    and w_min, so the far rows read footprint-weighted levels.  Not together with with_normal=True (NotImplementedError)."""
     rays = packed.march(grid, origin, dir, t_range, dt, cap, k_max=k_max)
-    rgb_s, dens_s = forward(P, cfg, rays.xyz, rays.dirs, spf=max(int(cap), 1), prec=prec, res=res, table_grad_f16=table_grad_f16)
+    rgb_s, dens_s = forward(P, cfg, rays.xyz, rays.dirs, spf=max(int(cap), 1), prec=prec, res=res, table_grad_f16=table_grad_f16,
+                            radius=_footprint_radius(rays, dir, footprint, with_normal), w_min=w_min)
     fields = {"rgb": rgb_s, "depth": rays.t[:, None]}
     if with_normal:
         fields["normal"] = normals(P, cfg, rays.xyz, res=res)
@@ -261,16 +308,19 @@ def update_occupancy_cascade(P, cfg, cascade, prec=mlp.PREC_F32, chunk=1 << 22, 
 
 
 def render_packed_cone(P, cfg, cascade, origin, dir, t_range, cone, dt_min, dt_max, cap, prec=mlp.PREC_F32, table_grad_f16=False, k_max=1024, res=None,
-                       with_normal=False, with_distortion=False):
+                       with_normal=False, with_distortion=False, footprint=None, w_min=1.0 / 256):
     """render_packed() with the cone-stepped march through a cascade of occupancy grids (include/lab4d_conemarch.h), for a scene box many
     times as wide as the object: packed.march_cone(cascade, origin, dir, t_range, cone, dt_min, dt_max, cap, k_max) steps every ray at
     s = clamp(a * cone, dt_min, dt_max) and keeps a candidate iff its bit is set at the cascade level that fits its position and its step;
     forward() runs on the kept rows (P["aabb"] is the cascade's outermost box; the parked rows lie outside it) and packed.composite renders
     them with each row's OWN delta = s |dir|.  Returns what render_packed returns: (rgb (R,3), mask (R,1), depth (R,1), total, overflow), then
     `normal (R,3)` with with_normal=True, then `distortion (R,1)` with with_distortion=True: packed.distortion with mid = t and width = steps
-    per row, in the units of t.  Gradients flow to the table, the Linears and logibeta."""
+    per row, in the units of t.  Gradients flow to the table, the Linears and logibeta.
+    footprint, w_min: as in render_packed -- the anti-aliased far field: a row at distance t reads level l times erf(1 / (sqrt(8) sigma n_l)) with
+    sigma = t |dir| footprint over the box's smallest edge, and nothing of the levels whose weight lies below w_min."""
     rays = packed.march_cone(cascade, origin, dir, t_range, cone, dt_min, dt_max, cap, k_max=k_max)
-    rgb_s, dens_s = forward(P, cfg, rays.xyz, rays.dirs, spf=max(int(cap), 1), prec=prec, res=res, table_grad_f16=table_grad_f16)
+    rgb_s, dens_s = forward(P, cfg, rays.xyz, rays.dirs, spf=max(int(cap), 1), prec=prec, res=res, table_grad_f16=table_grad_f16,
+                            radius=_footprint_radius(rays, dir, footprint, with_normal), w_min=w_min)
     fields = {"rgb": rgb_s, "depth": rays.t[:, None]}
     if with_normal:
         fields["normal"] = normals(P, cfg, rays.xyz, res=res)
